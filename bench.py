@@ -16,11 +16,18 @@ Multi-GPU is weak scaling of ONE estate: the global estate is N x the
 per-GPU size, every rank owns the node ids congruent to its rank
 (provably equal to a single-engine run on the same estate —
 tests/test_dist_engine.py).  value = aggregate findings/sec over all N
-GPUs.  After the timed region, p50 blast-radius query latency (the second
-BASELINE metric) is measured: single-GPU via hipGraph replay; multi-GPU
-via collective distributed bounded BFS queries.
+GPUs.
+
+A plain run does only what the headline figure needs: set up, warm up,
+time ``--steps`` steps, print the result line.  ``--full`` adds, after the
+timed region, the p50 blast-radius query latency (the second BASELINE
+metric): single-GPU via hipGraph replay; multi-GPU via collective
+distributed bounded BFS queries.  ``--dump-outputs DIR`` writes what the
+last timed step returned as ``DIR/<name>.npy`` so two builds can be
+compared output for output (same arguments -> same seeded estate).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--packages P]
+                       [--full] [--dump-outputs DIR]
 For N>1 the driver launches via torch.distributed.run (one rank per GPU).
 """
 
@@ -48,14 +55,56 @@ def parse_args():
                     help="advisory windows per GPU-worth of catalog (OSV-dump-"
                          "shaped: zipf branch counts, mixed window forms)")
     ap.add_argument("--queries", type=int, default=201,
-                    help="blast-radius latency queries after the timed region")
+                    help="blast-radius latency queries after the timed region "
+                         "(measured only with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure "
+                         "(p50 blast-radius query latency)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--device", default="cuda")
     return ap.parse_args()
 
 
+# --dump-outputs: arrays longer than this are written as a fixed, seeded
+# sample (9 arrays x 512Ki x 8 B = 36 MiB worst case, under the 64 MB cap)
+DUMP_MAX_ELEMS = 1 << 19
+DUMP_SAMPLE_SEED = 0x0D0FF
+
+
+def dump_outputs(res: dict, out_dir: str, suffix: str = "") -> None:
+    """Write every entry of a step result as ``out_dir/<name><suffix>.npy``.
+
+    Floating arrays are stored as float32, integer arrays and scalars as
+    float64 (exact for every index this pipeline produces).  An array of
+    more than DUMP_MAX_ELEMS elements is reduced to the elements at a sorted
+    index sample that depends only on its length, so equal-shaped outputs of
+    two builds are sampled at the same positions.
+    """
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, val in res.items():
+        if isinstance(val, torch.Tensor):
+            arr = val.detach().cpu().numpy().reshape(-1)
+        else:
+            arr = np.asarray([val])
+        if arr.size > DUMP_MAX_ELEMS:
+            rng = np.random.default_rng([DUMP_SAMPLE_SEED, arr.size])
+            pick = np.sort(rng.choice(arr.size, DUMP_MAX_ELEMS, replace=False))
+            arr = arr[pick]
+        dtype = np.float32 if arr.dtype.kind == "f" and arr.dtype.itemsize <= 4 \
+            else np.float64
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr.astype(dtype))
+
+
 def main():
     args = parse_args()
+    if args.steps < 1:
+        print("ERROR: --steps must be at least 1", file=sys.stderr)
+        sys.exit(2)
     import torch
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -147,9 +196,14 @@ def main():
     ms_per_step = elapsed / args.steps * 1000.0
     findings_per_sec = total_findings_per_step * args.steps / elapsed
 
-    # p50 blast-radius query latency
+    if args.dump_outputs:
+        dump_outputs(res, args.dump_outputs,
+                     suffix=f".rank{rank}" if distributed else "")
+
+    # p50 blast-radius query latency (--full only)
     p50_ms = None
-    if distributed and args.queries > 0:
+    measure_queries = args.full and args.queries > 0
+    if distributed and measure_queries:
         # collective distributed bounded-BFS queries: every rank participates,
         # rank 0 reports the median wall time per query
         qidx = torch.arange(args.queries, dtype=torch.int64) * 997 % est.n_packages
@@ -166,7 +220,7 @@ def main():
                 torch.cuda.synchronize()
             lat.append((time.perf_counter() - tq) * 1000.0)
         p50_ms = statistics.median(lat)
-    elif rank == 0 and args.queries > 0:
+    elif rank == 0 and measure_queries:
         rng_idx = torch.arange(args.queries, dtype=torch.int64) * 997 % est.n_packages
         nodes = (rng_idx + est.pkg_base).to(device)
         lat = []

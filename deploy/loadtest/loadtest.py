@@ -26,9 +26,14 @@ from __future__ import annotations
 import argparse
 import json
 import random
+import sys
 import threading
 import time
+from pathlib import Path
 from typing import Callable
+
+# runnable straight from a source checkout (no installed package needed)
+sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
 
 
 def _percentile(xs: list[float], q: float) -> float:

@@ -15,8 +15,12 @@ from __future__ import annotations
 import random
 import string
 import sys
+from pathlib import Path
 
-from agentbom_amd.scan.policy import evaluate_expression
+# runnable straight from a source checkout (no installed package needed)
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+
+from agentbom_amd.scan.policy import evaluate_expression  # noqa: E402
 
 
 class _Br:

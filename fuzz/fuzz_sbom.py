@@ -11,6 +11,10 @@ from __future__ import annotations
 import json
 import random
 import sys
+from pathlib import Path
+
+# runnable straight from a source checkout (no installed package needed)
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 
 
 def one_input(data: bytes) -> None:

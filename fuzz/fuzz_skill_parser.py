@@ -14,6 +14,9 @@ import sys
 import tempfile
 from pathlib import Path
 
+# runnable straight from a source checkout (no installed package needed)
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+
 
 def one_input(data: bytes) -> None:
     from agentbom_amd.scan.skills import scan_skills_tree

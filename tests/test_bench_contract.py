@@ -19,6 +19,8 @@ ROOT = Path(__file__).resolve().parents[1]
 ARGS = ["--device", "cpu", "--packages", "8000", "--agents", "200",
         "--servers", "800", "--name-catalog", "1500", "--arena-windows",
         "3000", "--steps", "2", "--warmup", "1", "--queries", "2"]
+# the query-latency figure is measured only with --full
+FULL_ARGS = [*ARGS, "--full"]
 
 REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup",
             "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -34,7 +36,7 @@ def _parse(stdout: str) -> dict:
 @pytest.mark.timeout(300)
 def test_single_process_contract():
     out = subprocess.run(
-        [sys.executable, str(ROOT / "bench.py"), *ARGS],
+        [sys.executable, str(ROOT / "bench.py"), *FULL_ARGS],
         capture_output=True, text=True, timeout=240, cwd=str(ROOT))
     assert out.returncode == 0, out.stderr[-800:]
     doc = _parse(out.stdout)
@@ -50,6 +52,34 @@ def test_single_process_contract():
     assert cfg["p50_blast_query_ms"] is not None
 
 
+@pytest.mark.timeout(300)
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full only the headline is measured; --dump-outputs writes
+    the last timed step's arrays as float32/float64 .npy files."""
+    import numpy as np
+
+    dump = tmp_path / "outputs"
+    out = subprocess.run(
+        [sys.executable, str(ROOT / "bench.py"), *ARGS,
+         "--dump-outputs", str(dump)],
+        capture_output=True, text=True, timeout=240, cwd=str(ROOT))
+    assert out.returncode == 0, out.stderr[-800:]
+    doc = _parse(out.stdout)
+    assert REQUIRED <= set(doc)
+    assert doc["steps"] == 2 and doc["value"] > 0 and doc["ms_per_step"] > 0
+    assert doc["config"]["p50_blast_query_ms"] is None
+    arrays = {p.stem: np.load(p) for p in dump.glob("*.npy")}
+    assert {"n_findings", "scores", "order", "pkg_idx", "win_idx", "n_agents",
+            "n_creds", "n_tools", "reach_dist"} <= set(arrays)
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    n = doc["config"]["findings_per_step"]
+    assert int(arrays["n_findings"][0]) == n
+    assert arrays["scores"].shape == (n,) and arrays["scores"].dtype == np.float32
+    assert sorted(arrays["order"].tolist()) == list(range(n))
+    assert arrays["reach_dist"].size == doc["config"]["nodes_global"]
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 1000 * 1000
+
+
 @pytest.mark.timeout(420)
 def test_distributed_launch_contract():
     with socket.socket() as s:
@@ -59,7 +89,7 @@ def test_distributed_launch_contract():
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2",
-         *ARGS],
+         *FULL_ARGS],
         capture_output=True, text=True, timeout=360, cwd=str(ROOT),
         env={**os.environ, "MASTER_ADDR": "127.0.0.1"})
     assert out.returncode == 0, out.stderr[-1200:]

@@ -113,8 +113,11 @@ class TestStoreAndSchedule:
         # no interval -> never polled; disabled -> never due
         c2 = store.put(CloudConnection(provider="aws", display_name="manual"))
         assert not c2.due(_NOW)
+        # mark_scanned stamps the real clock, so "a day later" is measured
+        # from that stamp, not from the fixed _NOW
         assert [d.connection_id for d in store.due_connections(
-            "default", at=_NOW + timedelta(days=1))] == [c.connection_id]
+            "default", at=datetime.fromisoformat(fresh.last_scan_at)
+            + timedelta(days=1))] == [c.connection_id]
 
 
 class TestApi:
