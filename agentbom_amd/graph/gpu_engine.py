@@ -5,7 +5,7 @@ forward and reverse CSR on-device (torch sort/bincount/cumsum — GPU CSR
 construction) and stays resident in HBM3E.  On top of it:
 
 - ``match()``            bulk advisory matching (ops/csrc/match.hip)
-- ``dependency_reach()`` multi-source BFS from all agents (graph.hip)
+- ``dependency_reach()`` multi-source BFS from all agents (ops/csrc/bfs.hip)
 - ``blast_counts()``     segmented joins: per-finding distinct agent/cred/
                          tool reach with CWE-impact filtering
 - ``score()``            GPU risk scoring (reference formula)
@@ -310,19 +310,13 @@ class EstateEngine:
         if self.use_gpu:
             from agentbom_amd.ops import native
 
-            torch = self.torch
             sp, sw = native.match(
                 self.pkg_group_key_sorted, self.pkg_key_hi_sorted,
                 self.pkg_key_lo_sorted, self.pkg_flags_sorted,
                 self.arena["group_keys"], self.arena["group_off"], self.arena["windows"],
                 pkg_win_range=self.pkg_win_range,
             )
-            # map sorted rows back to original package indices, re-sort for
-            # the deterministic (pkg, window) output order
-            orig = self.pkg_perm[sp]
-            packed = (orig << 32) | sw
-            packed, _ = torch.sort(packed)
-            return (packed >> 32), (packed & 0xFFFFFFFF)
+            return self._unsort_matches(sp, sw)
         # CPU oracle path (tests / dev boxes)
         from agentbom_amd.ops import cpu_ref
 
@@ -339,6 +333,14 @@ class EstateEngine:
             win,
         )
         return torch.from_numpy(pkg_i), torch.from_numpy(win_i)
+
+    def _unsort_matches(self, sp, sw):
+        """Map sorted match rows back to original package indices and re-sort
+        for the deterministic (pkg, window) output order."""
+        orig = self.pkg_perm[sp]
+        packed = (orig << 32) | sw
+        packed, _ = self.torch.sort(packed)
+        return (packed >> 32), (packed & 0xFFFFFFFF)
 
     def dependency_reach(self):
         """u32 hop distance from the nearest agent, per node (multi-source BFS)."""
@@ -520,10 +522,7 @@ class EstateEngine:
             if dd is not None:
                 pkg_idx, win_idx = expand_dedup_matches(torch, dd, sp, sw)
             else:
-                orig = self.pkg_perm[sp]
-                packed = (orig << 32) | sw
-                packed, _ = torch.sort(packed)
-                pkg_idx, win_idx = (packed >> 32), (packed & 0xFFFFFFFF)
+                pkg_idx, win_idx = self._unsort_matches(sp, sw)
         else:
             pkg_idx, win_idx = self.match()
             dist = reach_dist if reach_dist is not None else self.dependency_reach()
@@ -545,18 +544,28 @@ class EstateEngine:
                 self.arena["severity"], self.arena["kev"], self.arena["epss"],
                 self.arena["impact"], self.cred_lut, self.tool_lut,
                 counts["counts2d"].contiguous(), dist)
-            return {
-                "n_findings": int(n_findings),
-                "scores": scores,
-                "order": rank_order(torch, scores),
-                "pkg_idx": pkg_idx,
-                "win_idx": win_idx,
-                "n_agents": n_agents,
-                "n_creds": n_creds,
-                "n_tools": n_tools,
-                "reach_dist": dist,
-            }
+        else:
+            scores, n_agents, n_creds, n_tools = self._score_cpu(
+                counts, pos, pkg_nodes, win_idx, dist)
 
+        return {
+            "n_findings": int(n_findings),
+            "scores": scores,
+            # deterministic rank: quantized score desc, finding index asc
+            "order": rank_order(torch, scores),
+            "pkg_idx": pkg_idx,
+            "win_idx": win_idx,
+            "n_agents": n_agents,
+            "n_creds": n_creds,
+            "n_tools": n_tools,
+            "reach_dist": dist,
+        }
+
+    def _score_cpu(self, counts, pos, pkg_nodes, win_idx, dist):
+        """CPU oracle of the fused score_gather kernel: (scores, n_agents,
+        n_creds, n_tools) per finding."""
+        torch = self.torch
+        n_findings = win_idx.numel()
         # CWE-impact filtering via LUTs: 2=full, 1=db-only, 0=none
         impact = self.arena["impact"].to(torch.int64)[win_idx]
         cred_cls = self.cred_lut.to(torch.int64)[impact]
@@ -592,20 +601,7 @@ class EstateEngine:
                 flags.numpy(), epss.numpy(), scorecard.numpy(), reach.numpy(),
             )
         )
-
-        # deterministic rank: quantized score desc, finding index asc
-        order = rank_order(torch, scores)
-        return {
-            "n_findings": int(n_findings),
-            "scores": scores,
-            "order": order,
-            "pkg_idx": pkg_idx,
-            "win_idx": win_idx,
-            "n_agents": n_agents,
-            "n_creds": n_creds,
-            "n_tools": n_tools,
-            "reach_dist": dist,
-        }
+        return scores, n_agents, n_creds, n_tools
 
     def rollup(self, step_res=None):
         """Estate CONTAINS-tree collapse on device.
@@ -804,17 +800,13 @@ class EstateEngine:
         out_hops = torch.empty((batch, max_nodes), dtype=torch.uint8, device=dev)
         out_counts = torch.zeros(batch, dtype=torch.int32, device=dev)
         out_trunc = torch.zeros(batch, dtype=torch.uint8, device=dev)
-        lib = native.load()
-        import ctypes
 
         def _launch():
-            rc = lib.abom_impact_query(
-                native._ptr(self.rev["row_off"]), native._ptr(self.rev["col"]),
-                None, ctypes.c_uint(0xFFFFFFFF), native._ptr(q_in), batch,
-                max_hops, max_nodes, native._ptr(out_nodes),
-                native._ptr(out_hops), native._ptr(out_counts),
-                native._ptr(out_trunc), native._stream())
-            native._check(rc, "abom_impact_query")
+            # with ``out`` given this is the single abom_impact_query launch
+            native.impact_query(
+                self.rev["row_off"], self.rev["col"], q_in, etype=None,
+                allowed_mask=0xFFFFFFFF, max_hops=max_hops, max_nodes=max_nodes,
+                out=(out_nodes, out_hops, out_counts, out_trunc))
 
         # warmup on a side stream, then capture
         s = torch.cuda.Stream(device=dev)

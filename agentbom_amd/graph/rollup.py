@@ -5,7 +5,7 @@ Reference: src/agent_bom/graph/rollup.py:432 rollup_view / :583 drill_down /
 histograms, exposed/toxic flags; drill-down one level at a time.
 
 At estate scale the severity histograms run as the GPU segmented
-reduction (ops/csrc graph.hip severity_histogram_kernel).
+reduction (ops/csrc/score.hip severity_histogram_kernel).
 """
 
 from __future__ import annotations

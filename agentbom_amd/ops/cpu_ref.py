@@ -3,7 +3,7 @@
 These are the numerics oracle for the HIP kernels (tests/test_ops_gpu.py
 compares device results bit-for-bit / set-for-set against these) and the
 engine used on GPU-less development machines.  Semantics mirror
-ops/csrc/{match,graph}.hip exactly.
+ops/csrc/{match,bfs,query,score}.hip exactly.
 """
 
 from __future__ import annotations

@@ -1,0 +1,98 @@
+// The C ABI of _abom_gpu.so: every exported entry point, declared once.
+// Every csrc/*.hip file includes this header, so a definition that drifts
+// from its prototype stops compiling (C linkage cannot overload).
+// ops/native.py::_SIGNATURES mirrors it line for line for ctypes;
+// tests/test_native_abi.py parses this file to hold the two together.
+//
+// Device buffers travel as void* / const void*, counts as long long, `stream`
+// is a hipStream_t, and unless noted the int result is a hipError_t.  Only
+// void*, const void*, long long, unsigned int, int, double and const float*
+// appear as parameter types.
+#pragma once
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+// abom_api.hip
+int abom_abi_version();
+int abom_device_count();
+const char* abom_error_string(int code);
+
+// match.hip (w_packed, pkg_wbeg/pkg_wend and p_order are nullable)
+int abom_match(
+    const void* pkg_group_key, const void* pkg_key_hi, const void* pkg_key_lo,
+    const void* pkg_flags, long long num_packages,
+    const void* group_keys, const void* group_off, long long num_groups,
+    const void* w_intro_hi, const void* w_intro_lo, const void* w_fixed_hi, const void* w_fixed_lo,
+    const void* w_last_hi, const void* w_last_lo, const void* w_flags, const void* w_packed,
+    const void* pkg_wbeg, const void* pkg_wend, const void* p_order,
+    void* out_pairs, void* out_count, long long capacity, void* stream);
+
+// bfs.hip (abom_bfs_run returns the number of levels run or a negated hipError_t)
+int abom_bfs_expand(
+    const void* row_off, const void* col, const void* etype, unsigned int allowed_mask,
+    const void* frontier, long long frontier_size, void* dist, unsigned int next_level,
+    void* next_frontier, void* next_count, void* heavy_queue, void* heavy_count,
+    void* next_degree_sum, long long capacity, void* stream);
+int abom_bfs_expand_heavy(
+    const void* row_off, const void* col, const void* etype, unsigned int allowed_mask,
+    const void* heavy_queue, const void* heavy_size_ptr, void* dist, unsigned int next_level,
+    void* next_frontier, void* next_count, void* next_degree_sum, long long capacity,
+    void* stream);
+int abom_bfs_expand_edges(
+    const void* edge_src, const void* col, const void* etype, unsigned int allowed_mask,
+    long long num_edges, const void* row_off, void* dist, unsigned int cur_level,
+    void* next_frontier, void* next_count, void* next_degree_sum, int build_frontier,
+    long long capacity, void* stream);
+int abom_bfs_run(
+    const void* row_off, const void* col, const void* etype, unsigned int allowed_mask,
+    const void* sources, long long n_sources, void* dist, long long num_nodes,
+    void* frontier_a, void* frontier_b, void* heavy_queue, void* counters,
+    int max_levels, const void* edge_src, long long num_edges, double avg_degree,
+    const void* rev_off, const void* rev_col, const void* rev_et, void* stream);
+
+// query.hip
+int abom_impact_query(
+    const void* row_off, const void* col, const void* etype, unsigned int allowed_mask,
+    const void* query_sources, int num_queries, int max_hops, int max_nodes_per_query,
+    void* out_nodes, void* out_hops, void* out_counts, void* out_truncated, void* stream);
+
+// score.hip
+int abom_risk_score(
+    const void* severity, const void* n_agents, const void* n_creds, const void* n_tools,
+    const void* flags, const void* epss, const void* scorecard, const void* reach,
+    void* out, long long n, const float* weights22, void* stream);
+int abom_score_gather(
+    const void* win_idx, const void* pkg_nodes, const void* pos,
+    const void* a_sev, const void* a_kev, const void* a_epss, const void* a_impact,
+    const void* cred_lut, const void* tool_lut, const void* counts2d,
+    const void* dist, void* out_scores, void* out_agents, void* out_creds,
+    void* out_tools, long long n, const float* weights22, void* stream);
+int abom_severity_histogram(
+    const void* owner, const void* severity, void* hist, long long n, void* stream);
+
+// blast.hip
+int abom_blast_counts(
+    const void* pkgs, long long n,
+    const void* rev_off, const void* rev_col, const void* rev_et,
+    const void* fwd_off, const void* fwd_col, const void* fwd_et,
+    int et_contains, int et_uses, int et_cred, int et_tool,
+    const void* node_is_db_cred, const void* node_is_db_tool,
+    void* out_counts, void* out_overflow, void* stream);
+
+// paths.hip (edge_weight and node_gate are nullable)
+int abom_path_relax(
+    const void* edge_src, const void* col, const void* etype, const void* edge_weight,
+    const void* cur, void* nxt, const void* node_boost, const void* etype_boost,
+    const void* etype_trav, const void* etype_gate, const void* node_gate,
+    long long num_edges, void* stream);
+
+// rank.hip
+int abom_rank_order(
+    const void* scores, long long n, void* hist, void* bin_scratch, int nblocks,
+    void* order, void* stream);
+
+#ifdef __cplusplus
+}
+#endif

@@ -26,6 +26,13 @@ __device__ __forceinline__ bool key_gt(uint64_t ahi, uint64_t alo, uint64_t bhi,
     return key_lt(bhi, blo, ahi, alo);
 }
 
+// Edge-type filter of the graph walks: edge e is skipped when the graph
+// carries per-edge types and the type's bit is clear in allowed_mask.
+__device__ __forceinline__ bool edge_filtered(const uint8_t* __restrict__ etype,
+                                              uint32_t allowed_mask, uint64_t e) {
+    return etype && !((allowed_mask >> etype[e]) & 1u);
+}
+
 // Window flags (shared contract with agentbom_amd/db/arena.py)
 constexpr uint8_t WF_HAS_INTRO = 1u << 0;
 constexpr uint8_t WF_HAS_FIXED = 1u << 1;

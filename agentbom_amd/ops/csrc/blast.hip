@@ -14,6 +14,7 @@
 // (SRV_CAP + AG_CAP + CR_CAP + TL_CAP) * 4 B = 4.5 KiB -> 18 KiB/block,
 // sized so LDS is not the occupancy limiter (see cap comment below).
 
+#include "abom_api.h"
 #include "abom_common.h"
 
 namespace abom {

@@ -25,6 +25,7 @@
 // appended through a device atomic cursor as (pkg_idx << 32 | window_idx);
 // the caller sorts the pairs for deterministic downstream ordering.
 
+#include "abom_api.h"
 #include "abom_common.h"
 
 namespace abom {

@@ -22,6 +22,7 @@
 // Per-path scores are exact (computed along the path, never from partial
 // atomics), so float reproducibility holds regardless of relaxation order.
 
+#include "abom_api.h"
 #include "abom_common.h"
 
 namespace {

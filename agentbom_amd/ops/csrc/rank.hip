@@ -17,6 +17,7 @@
 // wave64 throughout: one wave per block, lockstep LDS (no atomics, no
 // __syncthreads in the inner loop).  Four small launches replace the
 // multi-kernel rocprim onesweep pipeline.
+#include "abom_api.h"
 #include "abom_common.h"
 
 namespace {

@@ -19,31 +19,94 @@ import numpy as np
 _SO_PATH = Path(__file__).resolve().parent / "_abom_gpu.so"
 _lib: Optional[ctypes.CDLL] = None
 
-_c = ctypes.c_void_p
-_i64 = ctypes.c_longlong
-_u32 = ctypes.c_uint
-_i32 = ctypes.c_int
+_c = ctypes.c_void_p      # void* / const void*
+_i64 = ctypes.c_longlong  # long long
+_u32 = ctypes.c_uint      # unsigned int
+_i32 = ctypes.c_int       # int
+_f64 = ctypes.c_double    # double
+_fp = ctypes.POINTER(ctypes.c_float)  # const float*
 
+# The C ABI as ctypes (argtypes, restype): one entry per prototype of
+# csrc/abom_api.h, one row per line of that prototype, arguments in order.
+# tests/test_native_abi.py asserts the two agree.
 _SIGNATURES = {
     "abom_abi_version": ([], _i32),
     "abom_device_count": ([], _i32),
-    "abom_synchronize": ([_c], _i32),
     "abom_error_string": ([_i32], ctypes.c_char_p),
-    "abom_match": ([_c] * 4 + [_i64] + [_c, _c, _i64] + [_c] * 7 + [_c] + [_c, _c] + [_c] + [_c, _c, _i64, _c], _i32),
-    "abom_bfs_init": ([_c, _i64, _c], _i32),
-    "abom_bfs_seed": ([_c, _i64, _c, _c, _c, _c, _c], _i32),
-    "abom_bfs_expand": ([_c, _c, _c, _u32, _c, _i64, _c, _u32, _c, _c, _c, _c, _c, _i64, _c], _i32),
-    "abom_bfs_expand_heavy": ([_c, _c, _c, _u32, _c, _c, _c, _u32, _c, _c, _c, _i64, _c], _i32),
-    "abom_bfs_run": ([_c, _c, _c, _u32, _c, _i64, _c, _i64, _c, _c, _c, _c, _i32, _c, _i64, ctypes.c_double, _c, _c, _c, _c, _c], _i32),
-    "abom_bfs_expand_edges": ([_c, _c, _c, _u32, _i64, _c, _c, _u32, _c, _c, _c, _i32, _i64, _c], _i32),
-    "abom_impact_query": ([_c, _c, _c, _u32, _c, _i32, _i32, _i32, _c, _c, _c, _c, _c], _i32),
-    "abom_risk_score": ([_c] * 8 + [_c, _i64, ctypes.POINTER(ctypes.c_float), _c], _i32),
-    "abom_blast_counts": ([_c, _i64] + [_c] * 6 + [_i32] * 4 + [_c] * 4 + [_c], _i32),
-    "abom_severity_histogram": ([_c, _c, _c, _i64, _c], _i32),
-    "abom_score_gather": ([_c] * 11 + [_c] * 4 + [_i64, ctypes.POINTER(ctypes.c_float), _c], _i32),
-    "abom_path_relax": ([_c] * 11 + [_i64, _c], _i32),
-    "abom_rank_order": ([_c, _i64, _c, _c, _i32, _c, _c], _i32),
+    "abom_match": ([
+        _c, _c, _c,        # pkg_group_key, pkg_key_hi, pkg_key_lo
+        _c, _i64,          # pkg_flags, num_packages
+        _c, _c, _i64,      # group_keys, group_off, num_groups
+        _c, _c, _c, _c,    # w_intro_hi, w_intro_lo, w_fixed_hi, w_fixed_lo
+        _c, _c, _c, _c,    # w_last_hi, w_last_lo, w_flags, w_packed
+        _c, _c, _c,        # pkg_wbeg, pkg_wend, p_order
+        _c, _c, _i64, _c,  # out_pairs, out_count, capacity, stream
+    ], _i32),
+    "abom_bfs_expand": ([
+        _c, _c, _c, _u32,    # row_off, col, etype, allowed_mask
+        _c, _i64, _c, _u32,  # frontier, frontier_size, dist, next_level
+        _c, _c, _c, _c,      # next_frontier, next_count, heavy_queue, heavy_count
+        _c, _i64, _c,        # next_degree_sum, capacity, stream
+    ], _i32),
+    "abom_bfs_expand_heavy": ([
+        _c, _c, _c, _u32,  # row_off, col, etype, allowed_mask
+        _c, _c, _c, _u32,  # heavy_queue, heavy_size_ptr, dist, next_level
+        _c, _c, _c, _i64,  # next_frontier, next_count, next_degree_sum, capacity
+        _c,                # stream
+    ], _i32),
+    "abom_bfs_expand_edges": ([
+        _c, _c, _c, _u32,    # edge_src, col, etype, allowed_mask
+        _i64, _c, _c, _u32,  # num_edges, row_off, dist, cur_level
+        _c, _c, _c, _i32,    # next_frontier, next_count, next_degree_sum, build_frontier
+        _i64, _c,            # capacity, stream
+    ], _i32),
+    "abom_bfs_run": ([
+        _c, _c, _c, _u32,      # row_off, col, etype, allowed_mask
+        _c, _i64, _c, _i64,    # sources, n_sources, dist, num_nodes
+        _c, _c, _c, _c,        # frontier_a, frontier_b, heavy_queue, counters
+        _i32, _c, _i64, _f64,  # max_levels, edge_src, num_edges, avg_degree
+        _c, _c, _c, _c,        # rev_off, rev_col, rev_et, stream
+    ], _i32),
+    "abom_impact_query": ([
+        _c, _c, _c, _u32,      # row_off, col, etype, allowed_mask
+        _c, _i32, _i32, _i32,  # query_sources, num_queries, max_hops, max_nodes_per_query
+        _c, _c, _c, _c, _c,    # out_nodes, out_hops, out_counts, out_truncated, stream
+    ], _i32),
+    "abom_risk_score": ([
+        _c, _c, _c, _c,     # severity, n_agents, n_creds, n_tools
+        _c, _c, _c, _c,     # flags, epss, scorecard, reach
+        _c, _i64, _fp, _c,  # out, n, weights22, stream
+    ], _i32),
+    "abom_score_gather": ([
+        _c, _c, _c,         # win_idx, pkg_nodes, pos
+        _c, _c, _c, _c,     # a_sev, a_kev, a_epss, a_impact
+        _c, _c, _c,         # cred_lut, tool_lut, counts2d
+        _c, _c, _c, _c,     # dist, out_scores, out_agents, out_creds
+        _c, _i64, _fp, _c,  # out_tools, n, weights22, stream
+    ], _i32),
+    "abom_severity_histogram": ([_c, _c, _c, _i64, _c], _i32),  # owner, severity, hist, n, stream
+    "abom_blast_counts": ([
+        _c, _i64,                # pkgs, n
+        _c, _c, _c,              # rev_off, rev_col, rev_et
+        _c, _c, _c,              # fwd_off, fwd_col, fwd_et
+        _i32, _i32, _i32, _i32,  # et_contains, et_uses, et_cred, et_tool
+        _c, _c,                  # node_is_db_cred, node_is_db_tool
+        _c, _c, _c,              # out_counts, out_overflow, stream
+    ], _i32),
+    "abom_path_relax": ([
+        _c, _c, _c, _c,  # edge_src, col, etype, edge_weight
+        _c, _c, _c, _c,  # cur, nxt, node_boost, etype_boost
+        _c, _c, _c,      # etype_trav, etype_gate, node_gate
+        _i64, _c,        # num_edges, stream
+    ], _i32),
+    "abom_rank_order": ([
+        _c, _i64, _c, _c, _i32,  # scores, n, hist, bin_scratch, nblocks
+        _c, _c,                  # order, stream
+    ], _i32),
 }
+
+# Byte offsets into the BFS ``counters`` buffer (u32 slots of csrc/bfs.hip)
+_CTR_NEXT, _CTR_HEAVY, _CTR_DEGREE = 0, 4, 8
 
 
 class NativeUnavailable(RuntimeError):
@@ -109,6 +172,18 @@ def _stream() -> ctypes.c_void_p:
     import torch
 
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _buf(ws: dict, key: str, numel: int, dtype, dev, zero: bool = False):
+    """Workspace buffer ``ws[key]`` with room for ``numel`` elements: reused
+    when large enough, otherwise (re)allocated and stored back."""
+    import torch
+
+    t = ws.get(key)
+    if t is None or t.numel() < numel:
+        t = (torch.zeros if zero else torch.empty)(numel, dtype=dtype, device=dev)
+        ws[key] = t
+    return t
 
 
 # ── High-level ops (torch tensors on cuda device) ──────────────────────────
@@ -211,42 +286,16 @@ def bfs(row_off, col, sources, num_nodes: int, etype=None, allowed_mask: int = 0
 
     lib = load()
     dev = row_off.device
-    ws = workspace or {}
-    dist = ws.get("dist")
-    if dist is None or dist.numel() < num_nodes:
-        dist = torch.empty(num_nodes, dtype=torch.int32, device=dev)
-    fa = ws.get("frontier_a")
-    if fa is None or fa.numel() < num_nodes:
-        fa = torch.empty(num_nodes, dtype=torch.int32, device=dev)
-    fb = ws.get("frontier_b")
-    if fb is None or fb.numel() < num_nodes:
-        fb = torch.empty(num_nodes, dtype=torch.int32, device=dev)
-    hq = ws.get("heavy")
-    if hq is None or hq.numel() < num_nodes:
-        hq = torch.empty(num_nodes, dtype=torch.int32, device=dev)
-    ctr = ws.get("counters")
-    if ctr is None or ctr.numel() < 4:
-        ctr = torch.zeros(4, dtype=torch.int32, device=dev)
-    # dense-mode bitmaps: 3 x ceil(N/32) u32 words, L2/LLC-resident
-    bit_words = (num_nodes + 31) // 32
-    bits = ws.get("bits")
-    if bits is None or bits.numel() < 3 * bit_words:
-        bits = torch.empty(3 * bit_words, dtype=torch.int32, device=dev)
-    if workspace is not None:
-        workspace.update(dist=dist, frontier_a=fa, frontier_b=fb, heavy=hq,
-                         counters=ctr, bits=bits)
+    ws = workspace if workspace is not None else {}
+    dist = _buf(ws, "dist", num_nodes, torch.int32, dev)
+    fa = _buf(ws, "frontier_a", num_nodes, torch.int32, dev)
+    fb = _buf(ws, "frontier_b", num_nodes, torch.int32, dev)
+    hq = _buf(ws, "heavy", num_nodes, torch.int32, dev)
+    ctr = _buf(ws, "counters", 4, torch.int32, dev, zero=True)
 
     et = _ptr(etype) if etype is not None else None
     if os.environ.get("AGENT_BOM_BFS_DENSE", "1") == "0":
         edge_src = None  # A/B toggle: disable edge-centric dense-frontier mode
-    # Bitmap dense mode measured 2x SLOWER than dist-probe mode on MI355X:
-    # atomicOr packs 32 nodes per cache line and the 8 XCDs' private L2s
-    # ping-pong those shared lines through the coherence point, while the
-    # scattered dist[] writes touch each line once.  Kept behind an opt-in
-    # flag for future single-XCD / small-graph experiments.
-    bits_ptr = None
-    if os.environ.get("AGENT_BOM_BFS_BITS", "0") == "1":
-        bits_ptr = _ptr(bits)
     es = _ptr(edge_src) if edge_src is not None else None
     num_edges = col.numel()
     avg_degree = num_edges / max(num_nodes, 1)
@@ -260,7 +309,7 @@ def bfs(row_off, col, sources, num_nodes: int, etype=None, allowed_mask: int = 0
         _ptr(row_off), _ptr(col), et, allowed_mask,
         _ptr(sources), sources.numel(), _ptr(dist), num_nodes,
         _ptr(fa), _ptr(fb), _ptr(hq), _ptr(ctr), max_levels,
-        es, num_edges, float(avg_degree), bits_ptr,
+        es, num_edges, float(avg_degree),
         rev_off_p, rev_col_p, rev_et_p, _stream(),
     )
     if rc < 0:
@@ -282,30 +331,22 @@ def bfs_level(row_off, col, frontier, dist, level: int, etype=None,
     dev = row_off.device
     ws = workspace if workspace is not None else {}
     cap = dist.numel()
-    nxt = ws.get("next")
-    if nxt is None or nxt.numel() < cap:
-        nxt = torch.empty(cap, dtype=torch.int32, device=dev)
-        ws["next"] = nxt
-    hq = ws.get("heavy")
-    if hq is None or hq.numel() < max(frontier.numel(), 1):
-        hq = torch.empty(max(frontier.numel(), 1024), dtype=torch.int32, device=dev)
-        ws["heavy"] = hq
-    ctr = ws.get("counters")
-    if ctr is None or ctr.numel() < 4:
-        ctr = torch.zeros(4, dtype=torch.int32, device=dev)
-        ws["counters"] = ctr
+    nxt = _buf(ws, "next", cap, torch.int32, dev)
+    hq = _buf(ws, "heavy", max(frontier.numel(), 1024), torch.int32, dev)
+    ctr = _buf(ws, "counters", 4, torch.int32, dev, zero=True)
     ctr.zero_()
     et = _ptr(etype) if etype is not None else None
-    deg_ptr = ctypes.c_void_p(ctr.data_ptr() + 8)
+    next_ptr, heavy_ptr, deg_ptr = (
+        ctypes.c_void_p(ctr.data_ptr() + off) for off in (_CTR_NEXT, _CTR_HEAVY, _CTR_DEGREE))
     rc = lib.abom_bfs_expand(
         _ptr(row_off), _ptr(col), et, allowed_mask, _ptr(frontier), frontier.numel(),
-        _ptr(dist), level, _ptr(nxt), _ptr(ctr), _ptr(hq),
-        ctypes.c_void_p(ctr.data_ptr() + 4), deg_ptr, cap, _stream(),
+        _ptr(dist), level, _ptr(nxt), next_ptr, _ptr(hq),
+        heavy_ptr, deg_ptr, cap, _stream(),
     )
     _check(rc, "abom_bfs_expand")
     rc = lib.abom_bfs_expand_heavy(
         _ptr(row_off), _ptr(col), et, allowed_mask, _ptr(hq),
-        ctypes.c_void_p(ctr.data_ptr() + 4), _ptr(dist), level, _ptr(nxt), _ptr(ctr),
+        heavy_ptr, _ptr(dist), level, _ptr(nxt), next_ptr,
         deg_ptr, cap, _stream(),
     )
     _check(rc, "abom_bfs_expand_heavy")
@@ -330,20 +371,15 @@ def bfs_level_edges(row_off, col, edge_src, frontier_dist_level: int, dist,
     dev = row_off.device
     ws = workspace if workspace is not None else {}
     cap = dist.numel()
-    nxt = ws.get("next")
-    if nxt is None or nxt.numel() < cap:
-        nxt = torch.empty(cap, dtype=torch.int32, device=dev)
-        ws["next"] = nxt
-    ctr = ws.get("counters")
-    if ctr is None or ctr.numel() < 4:
-        ctr = torch.zeros(4, dtype=torch.int32, device=dev)
-        ws["counters"] = ctr
+    nxt = _buf(ws, "next", cap, torch.int32, dev)
+    ctr = _buf(ws, "counters", 4, torch.int32, dev, zero=True)
     ctr.zero_()
     et = _ptr(etype) if etype is not None else None
     rc = lib.abom_bfs_expand_edges(
         _ptr(edge_src), _ptr(col), et, allowed_mask, col.numel(),
-        _ptr(row_off), _ptr(dist), frontier_dist_level, _ptr(nxt), _ptr(ctr),
-        ctypes.c_void_p(ctr.data_ptr() + 8), 1, cap, _stream(),
+        _ptr(row_off), _ptr(dist), frontier_dist_level, _ptr(nxt),
+        ctypes.c_void_p(ctr.data_ptr() + _CTR_NEXT),
+        ctypes.c_void_p(ctr.data_ptr() + _CTR_DEGREE), 1, cap, _stream(),
     )
     _check(rc, "abom_bfs_expand_edges")
     n = int(ctr[0].item())
@@ -351,21 +387,25 @@ def bfs_level_edges(row_off, col, edge_src, frontier_dist_level: int, dist,
 
 
 def impact_query(row_off, col, query_sources, etype=None, allowed_mask: int = 0xFFFFFFFF,
-                 max_hops: int = 4, max_nodes: int = 4096):
+                 max_hops: int = 4, max_nodes: int = 4096, out=None):
     """Batched bounded blast-radius queries (one block per query).
 
     Returns (nodes u32 [Q, max_nodes], hops u8 [Q, max_nodes], counts u32 [Q],
-    truncated u8 [Q]).
+    truncated u8 [Q]).  ``out`` may carry those four tensors preallocated; the
+    call then allocates nothing and is exactly one kernel launch, which is
+    what a hipGraph capture needs.
     """
     import torch
 
     lib = load()
     dev = row_off.device
     Q = query_sources.numel()
-    out_nodes = torch.empty((Q, max_nodes), dtype=torch.int32, device=dev)
-    out_hops = torch.empty((Q, max_nodes), dtype=torch.uint8, device=dev)
-    out_counts = torch.zeros(Q, dtype=torch.int32, device=dev)
-    out_trunc = torch.zeros(Q, dtype=torch.uint8, device=dev)
+    if out is None:
+        out = (torch.empty((Q, max_nodes), dtype=torch.int32, device=dev),
+               torch.empty((Q, max_nodes), dtype=torch.uint8, device=dev),
+               torch.zeros(Q, dtype=torch.int32, device=dev),
+               torch.zeros(Q, dtype=torch.uint8, device=dev))
+    out_nodes, out_hops, out_counts, out_trunc = out
     et = _ptr(etype) if etype is not None else None
     rc = lib.abom_impact_query(
         _ptr(row_off), _ptr(col), et, allowed_mask, _ptr(query_sources), Q,
@@ -511,14 +551,8 @@ def rank_bucket_order(scores, workspace: Optional[dict] = None):
         return torch.empty(0, dtype=torch.int64, device=dev)
     nblocks = (n + _RANK_CHUNK - 1) // _RANK_CHUNK
     ws = workspace if workspace is not None else {}
-    hist = ws.get("rank_hist")
-    if hist is None or hist.numel() < nblocks * _RANK_BINS:
-        hist = torch.empty(nblocks * _RANK_BINS, dtype=torch.int32, device=dev)
-        ws["rank_hist"] = hist
-    scratch = ws.get("rank_scratch")
-    if scratch is None:
-        scratch = torch.empty(2 * _RANK_BINS, dtype=torch.int32, device=dev)
-        ws["rank_scratch"] = scratch
+    hist = _buf(ws, "rank_hist", nblocks * _RANK_BINS, torch.int32, dev)
+    scratch = _buf(ws, "rank_scratch", 2 * _RANK_BINS, torch.int32, dev)
     order = torch.empty(n, dtype=torch.int64, device=dev)
     rc = lib.abom_rank_order(_ptr(scores), n, _ptr(hist), _ptr(scratch),
                              nblocks, _ptr(order), _stream())

@@ -93,6 +93,118 @@ def test_bfs_parity(estate, dev):
     assert np.array_equal(dist_gpu, dist_cpu)
 
 
+# ── level-loop arms: a hand-built graph that drives every mode switch ───────
+#
+# 0 -> 1 -> 8192 leaves; leaf 2 -> chain c0..c5; c2 is a heavy vertex (100
+# back edges to visited leaves); 3 -> 8200 by a type-5 edge; 8201 isolated.
+# N=8202, E=8300: E/8 ~ 1037 (dense entry), E/4096 ~ 2.03 (hand-back).  With
+# edge_src the loop runs sparse, dense, dense (1 claim -> hand-back),
+# collect_frontier, then sparse to level 9 with the heavy queue at level 6.
+
+_ARM_LEAVES = 8192
+_ARM_C0 = 2 + _ARM_LEAVES
+_ARM_BLOCKED = _ARM_C0 + 6
+_ARM_N = _ARM_BLOCKED + 2
+
+
+def _arm_edges():
+    edges = [(0, 1, 0)]
+    edges += [(1, leaf, 0) for leaf in range(2, 2 + _ARM_LEAVES)]
+    edges.append((2, _ARM_C0, 0))
+    for k in range(5):
+        if k == 2:
+            edges += [(_ARM_C0 + k, leaf, 0) for leaf in range(2, 102)]
+        edges.append((_ARM_C0 + k, _ARM_C0 + k + 1, 0))
+    edges.append((3, _ARM_BLOCKED, 5))
+    src, dst, et = (np.asarray(c) for c in zip(*edges))
+    return src.astype(np.int64), dst.astype(np.int64), et.astype(np.uint8)
+
+
+def _np_csr(src, dst, et, n):
+    """CSR by stable sort on source (as EstateEngine._build_csr)."""
+    order = np.argsort(src, kind="stable")
+    row_off = np.zeros(n + 1, dtype=np.int64)
+    row_off[1:] = np.cumsum(np.bincount(src, minlength=n))
+    return {"row_off": row_off, "col": dst[order].astype(np.int32),
+            "etype": et[order], "src": src[order].astype(np.int32)}
+
+
+def _to_dev(csr, dev):
+    return {k: torch.from_numpy(v).to(dev) for k, v in csr.items()}
+
+
+@pytest.fixture(scope="module")
+def arm_graph(dev):
+    from agentbom_amd.ops import cpu_ref
+
+    src, dst, et = _arm_edges()
+    assert len(src) == 8300 and _ARM_N == 8202
+    fwd = _np_csr(src, dst, et, _ARM_N)
+    small = (src < 16) & (dst < 16)
+    sub = _np_csr(src[small], dst[small], et[small], 16)
+
+    def ref(csr, n, mask, max_levels=64):
+        return cpu_ref.bfs(csr["row_off"], csr["col"], np.array([0]), n,
+                           etype=csr["etype"], allowed_mask=mask,
+                           max_levels=max_levels)
+
+    return {
+        "fwd": _to_dev(fwd, dev),
+        "rev": _to_dev(_np_csr(dst, src, et, _ARM_N), dev),
+        "sub": _to_dev(sub, dev),
+        "sub_rev": _to_dev(_np_csr(dst[small], src[small], et[small], 16), dev),
+        "ref": ref(fwd, _ARM_N, 0x1),
+        "ref_all": ref(fwd, _ARM_N, 0xFFFFFFFF),
+        "ref_l3": ref(fwd, _ARM_N, 0x1, max_levels=3),
+        "ref_sub": ref(sub, 16, 0x1),
+    }
+
+
+def _arm_bfs(dev, fwd, rev, mode, n, sources=(0,), **kw):
+    from agentbom_amd.ops import native
+
+    dist = native.bfs(
+        fwd["row_off"], fwd["col"],
+        torch.tensor(list(sources), dtype=torch.int32, device=dev), n,
+        etype=fwd["etype"],
+        edge_src=None if mode == "sparse" else fwd["src"],
+        rev=rev if mode == "bottom_up" else None, **kw)
+    return dist.cpu().numpy().view(np.uint32)
+
+
+@pytest.mark.parametrize("mode", ["sparse", "bottom_up", "edge_dense"])
+def test_bfs_level_loop_arms(arm_graph, dev, mode):
+    """native.bfs == cpu_ref.bfs through every arm of the level loop:
+    all-sparse (heavy queue takes the 8192-claim level), bottom-up dense and
+    edge-centric dist-driven dense, the last two handing back to sparse."""
+    g = arm_graph
+
+    def run(**kw):
+        return _arm_bfs(dev, g["fwd"], g["rev"], mode, _ARM_N, **kw)
+
+    dist = run(allowed_mask=0x1)
+    assert np.array_equal(dist, g["ref"])
+    assert dist[_ARM_BLOCKED] == 0xFFFFFFFF and dist[_ARM_N - 1] == 0xFFFFFFFF
+    assert dist[dist != 0xFFFFFFFF].max() == 8
+
+    # every edge type allowed: the type-5 edge is followed
+    dist = run(allowed_mask=0xFFFFFFFF)
+    assert np.array_equal(dist, g["ref_all"])
+    assert dist[_ARM_BLOCKED] == 3
+
+    assert np.array_equal(run(allowed_mask=0x1, max_levels=3), g["ref_l3"])
+    assert np.array_equal(run(allowed_mask=0x1, sources=(0, 0)), g["ref"])
+
+    # one workspace: two calls here, then a 16-node graph in the same
+    # (now larger than num_nodes) buffers
+    ws: dict = {}
+    for _ in range(2):
+        assert np.array_equal(run(allowed_mask=0x1, workspace=ws), g["ref"])
+    sub = _arm_bfs(dev, g["sub"], g["sub_rev"], mode, 16, allowed_mask=0x1,
+                   workspace=ws)
+    assert np.array_equal(sub, g["ref_sub"])
+
+
 def test_impact_query_parity(estate, dev):
     from agentbom_amd.graph.gpu_engine import EstateEngine
     from agentbom_amd.ops import cpu_ref
