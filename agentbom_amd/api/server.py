@@ -18,7 +18,7 @@ import os
 import threading
 import uuid
 from datetime import datetime, timezone
-from typing import Any, Optional
+from typing import Any, Literal, Optional
 
 from fastapi import Depends, FastAPI, Header, HTTPException, Request
 from pydantic import BaseModel, Field
@@ -581,16 +581,36 @@ def create_app() -> FastAPI:
         return {"node": g.nodes[node_id].to_dict(), "edges": edges}
 
     @app.get("/v1/graph/centrality", dependencies=[Depends(auth)])
-    def graph_centrality(request: Request, top_n: int = 20) -> dict:
+    def graph_centrality(
+            request: Request, top_n: int = 20,
+            metric: Literal["degree", "pagerank", "betweenness"] = "degree",
+            sample: int = 64, backend: Optional[str] = None) -> dict:
+        """Top nodes by degree (default), PageRank or Brandes betweenness;
+        the latter two run on the analytics backend (graph/backend.py)."""
         g = _latest_graph(request)
-        return {"centrality": [{"id": nid, "degree": deg}
-                               for nid, deg in g.degree_centrality(top_n)]}
+        if metric == "degree":
+            return {"centrality": [{"id": nid, "degree": deg}
+                                   for nid, deg in g.degree_centrality(top_n)]}
+        if metric == "pagerank":
+            scores = g.pagerank(backend=backend)
+        else:
+            scores = g.betweenness(sample=min(sample, 256), backend=backend)
+        top = sorted(scores.items(), key=lambda kv: (-kv[1], kv[0]))[:top_n]
+        return {"metric": metric,
+                "centrality": [{"id": nid, "score": score} for nid, score in top]}
 
     @app.get("/v1/graph/bottlenecks", dependencies=[Depends(auth)])
-    def graph_bottlenecks(request: Request, top_n: int = 10,
-                          sample: int = 64) -> dict:
-        """Approx-betweenness choke points (lateral-movement bottlenecks)."""
+    def graph_bottlenecks(request: Request, top_n: int = 10, sample: int = 64,
+                          method: Literal["approx", "brandes"] = "approx",
+                          backend: Optional[str] = None) -> dict:
+        """Choke points (lateral-movement bottlenecks): the cheap BFS-tree
+        approximation by default, Brandes betweenness with method=brandes."""
         g = _latest_graph(request)
+        if method == "brandes":
+            scores = g.betweenness(sample=min(sample, 256), backend=backend)
+            rows = sorted(scores.items(), key=lambda kv: (-kv[1], kv[0]))[:top_n]
+            return {"method": method,
+                    "bottlenecks": [{"id": nid, "score": score} for nid, score in rows]}
         rows = g.bottlenecks(top_n=top_n, sample=min(sample, 256))
         return {"bottlenecks": [{"id": nid, "score": round(score, 4)}
                                 for nid, score in rows]}

@@ -6,7 +6,9 @@ built-in approximations otherwise.  MI355X build ships a NATIVE numpy
 backend as the default (power-iteration PageRank, Brandes betweenness on a
 bounded sample) so the analytics work in the air-gapped image where
 networkx is absent; the NetworkX adapter remains for environments that
-have it (``AGENT_BOM_GRAPH_BACKEND=networkx``).
+have it (``AGENT_BOM_GRAPH_BACKEND=networkx``).  ``hip`` runs the same two
+analytics as HIP kernels (ops/csrc/centrality.hip) where a GPU and the built
+engine are present.
 """
 
 from __future__ import annotations
@@ -151,11 +153,102 @@ class NetworkXBackend:
         return dict(self._nx.betweenness_centrality(g, k=k, seed=7))
 
 
+def brandes_sources(n: int, sample: int) -> range:
+    """NativeBackend's deterministic source sample: every node when
+    ``sample >= n``, else every ``n // sample``-th (which can yield more than
+    ``sample`` sources)."""
+    return range(n) if sample >= n else range(0, n, max(1, n // sample))
+
+
+def traversable_edges(graph) -> tuple[list[str], np.ndarray, np.ndarray]:
+    """(ids, src, dst) exactly as NativeBackend walks a graph: nodes in
+    sorted-id order, traversable edges only, a bidirectional edge in both
+    directions, parallel edges kept, edge order as iterated."""
+    ids, pos = NativeBackend._index(graph)
+    src_idx, dst_idx = [], []
+    for e in graph.edges:
+        if getattr(e, "traversable", True):
+            src_idx.append(pos[e.source])
+            dst_idx.append(pos[e.target])
+            if getattr(e, "bidirectional", False):
+                src_idx.append(pos[e.target])
+                dst_idx.append(pos[e.source])
+    return (ids, np.asarray(src_idx, dtype=np.int64),
+            np.asarray(dst_idx, dtype=np.int64))
+
+
+def csr_arrays(rows: np.ndarray, cols: np.ndarray, n: int) -> tuple[np.ndarray, np.ndarray]:
+    """(row_off int64 [n+1], col int32 [E]) of the edges rows -> cols; the
+    edges of one row keep their input order."""
+    order = np.argsort(rows, kind="stable")
+    row_off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=n), out=row_off[1:])
+    return row_off, cols[order].astype(np.int32)
+
+
+class HipBackend:
+    """The NativeBackend analytics on the GPU (ops/csrc/centrality.hip), with
+    the same index, edge set and result contracts (traversable_edges)."""
+
+    name = "hip"
+
+    @staticmethod
+    def _csr(rows: np.ndarray, cols: np.ndarray, n: int) -> dict:
+        import torch
+
+        row_off, col = csr_arrays(rows, cols, n)
+        dev = torch.device("cuda")
+        return {"row_off": torch.from_numpy(row_off).to(dev),
+                "col": torch.from_numpy(col).to(dev)}
+
+    def pagerank(self, graph, damping: float = 0.85,
+                 iterations: int = 50) -> dict[str, float]:
+        import torch
+
+        from agentbom_amd.ops import native
+
+        ids, src, dst = traversable_edges(graph)
+        n = len(ids)
+        if n == 0:
+            return {}
+        rev = self._csr(dst, src, n)
+        out_degree = torch.from_numpy(
+            np.bincount(src, minlength=n).astype(np.int32)).to(rev["col"].device)
+        rank = native.pagerank(rev["row_off"], rev["col"], out_degree, n,
+                               damping=damping, iterations=iterations).cpu().numpy()
+        return {nid: float(rank[i]) for i, nid in enumerate(ids)}
+
+    def betweenness(self, graph, sample: int = 64) -> dict[str, float]:
+        from agentbom_amd.ops import native
+
+        ids, src, dst = traversable_edges(graph)
+        n = len(ids)
+        if n < 3:
+            return dict.fromkeys(ids, 0.0)
+        fwd = self._csr(src, dst, n)
+        rev = self._csr(dst, src, n)
+        bc = native.betweenness(fwd, rev, n, brandes_sources(n, sample)).cpu().numpy()
+        bc = bc / ((n - 1) * (n - 2))
+        return {nid: float(bc[i]) for i, nid in enumerate(ids)}
+
+
+def _hip_usable() -> bool:
+    try:
+        import torch
+
+        from agentbom_amd.ops import native
+
+        return bool(torch.cuda.is_available()) and native.available()
+    except Exception:
+        return False
+
+
 def get_backend(name: str | None = None) -> GraphBackendProtocol:
     """Resolve the analytics backend: arg > $AGENT_BOM_GRAPH_BACKEND > native.
 
-    Asking for networkx where it isn't installed falls back to native with
-    the same results contract (never an ImportError at call time).
+    Asking for networkx where it isn't installed, or for hip without a GPU
+    and the built engine, falls back to native with the same results
+    contract (never an ImportError at call time).
     """
     name = (name or os.environ.get("AGENT_BOM_GRAPH_BACKEND") or "native").lower()
     if name == "networkx":
@@ -163,4 +256,6 @@ def get_backend(name: str | None = None) -> GraphBackendProtocol:
             return NetworkXBackend()
         except ImportError:
             return NativeBackend()
+    if name == "hip" and _hip_usable():
+        return HipBackend()
     return NativeBackend()

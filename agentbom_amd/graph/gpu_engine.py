@@ -13,6 +13,8 @@ construction) and stays resident in HBM3E.  On top of it:
                          score -> rank (the bench.py timed region)
 - ``blast_radius_query()`` batched bounded BFS for p50 query latency /
                          the /v1/graph read path
+- ``pagerank()`` / ``betweenness()`` / ``choke_points()`` centrality on
+                         the resident CSR (ops/csrc/centrality.hip)
 
 Replaces the reference's scan_packages hot loop + graph dict walks
 (reference: src/agent_bom/scanners/package_scan.py:1307-2028,
@@ -866,3 +868,67 @@ class EstateEngine:
             out_counts[qi] = len(items)
             out_trunc[qi] = 1 if trunc else 0
         return out_nodes, out_hops, out_counts, out_trunc
+
+    # ── centrality on the resident estate (ops/csrc/centrality.hip) ────────
+
+    def _centrality_ws(self) -> dict:
+        ws = getattr(self, "_cen_ws", None)
+        if ws is None:
+            ws = self._cen_ws = {}
+        return ws
+
+    def pagerank(self, damping: float = 0.85, iterations: int = 50):
+        """PageRank over every estate edge; fp64 tensor [N] on the engine's
+        device.  Dangling mass (packages, credentials, tools) is spread
+        uniformly, as in graph/backend.py."""
+        torch = self.torch
+        out_degree = (self.fwd["row_off"][1:] - self.fwd["row_off"][:-1]).to(torch.int32)
+        if self.use_gpu:
+            from agentbom_amd.ops import native
+
+            return native.pagerank(self.rev["row_off"], self.rev["col"], out_degree, self.N,
+                                   damping=damping, iterations=iterations,
+                                   workspace=self._centrality_ws())
+        from agentbom_amd.ops import cpu_ref
+
+        return torch.from_numpy(cpu_ref.pagerank(
+            self.rev["row_off"].numpy(), self.rev["col"].numpy(), out_degree.numpy(),
+            self.N, damping=damping, iterations=iterations))
+
+    def betweenness(self, sample: int = 64, allowed_mask: Optional[int] = None):
+        """Brandes betweenness from the deterministic source sample of
+        graph/backend.py (exact when ``sample >= N``), divided by
+        (N-1)(N-2); fp64 tensor [N].  ``allowed_mask`` keeps only the edge
+        types whose bit is set (None walks every edge)."""
+        from agentbom_amd.graph.backend import brandes_sources
+
+        torch = self.torch
+        n = self.N
+        if n < 3:
+            return torch.zeros(n, dtype=torch.float64, device=self.device)
+        sources = brandes_sources(n, sample)
+        if self.use_gpu:
+            from agentbom_amd.ops import native
+
+            bc = native.betweenness(self.fwd, self.rev, n, sources,
+                                    workspace=self._centrality_ws(),
+                                    allowed_mask=allowed_mask)
+        else:
+            from agentbom_amd.ops import cpu_ref
+
+            masked = allowed_mask is not None
+            bc = torch.from_numpy(cpu_ref.betweenness(
+                self.fwd["row_off"].numpy(), self.fwd["col"].numpy(), n, sources,
+                etype=self.fwd["etype"].numpy() if masked else None,
+                allowed_mask=allowed_mask if masked else 0xFFFFFFFF))
+        return bc / float((n - 1) * (n - 2))
+
+    def choke_points(self, k: int = 20, sample: int = 64):
+        """The k nodes most shortest paths funnel through: (node_ids int64 [k],
+        scores fp64 [k]) by descending betweenness, ties by ascending id."""
+        scores = self.betweenness(sample=sample)
+        # a stable ascending sort of the negated scores keeps equal scores
+        # in ascending-id order
+        _neg, order = self.torch.sort(-scores, stable=True)
+        top = order[:k]
+        return top, scores[top]

@@ -241,3 +241,102 @@ def path_relax(edge_src, col, etype, edge_weight, cur, node_boost,
         cand = path_pack(s, e_idx[m])
         np.maximum.at(nxt, v[m] * 2 + 1, cand)
     return nxt
+
+
+# ── centrality (oracle for csrc/centrality.hip) ─────────────────────────────
+
+PAGERANK_TOLERANCE = 1e-10
+
+
+def _row_ids(row_off, num_nodes: int):
+    """Owning row of every CSR slot, in CSR order."""
+    deg = np.diff(np.asarray(row_off, dtype=np.int64))
+    return np.repeat(np.arange(num_nodes, dtype=np.int64), deg)
+
+
+def pagerank(rev_off, rev_col, out_degree, num_nodes: int, damping: float = 0.85,
+             iterations: int = 50):
+    """Pull power iteration over the reverse CSR; fp64 [N].
+
+    new[v] = (1-d)/n + d * sum_{u in in(v)} rank[u]/outdeg[u] + d * dangling/n,
+    with the in-neighbour sum taken in CSR order.  Stops after ``iterations``
+    passes or after the first pass whose L1 change is below 1e-10.
+    """
+    n = int(num_nodes)
+    if n == 0:
+        return np.zeros(0, dtype=np.float64)
+    dst = _row_ids(rev_off, n)
+    src = np.asarray(rev_col, dtype=np.int64)
+    out_deg = np.asarray(out_degree, dtype=np.float64)
+    dangling_nodes = out_deg == 0
+    rank = np.full(n, 1.0 / n)
+    teleport = (1.0 - damping) / n
+    for _ in range(iterations):
+        contrib = np.where(dangling_nodes, 0.0, rank / np.maximum(out_deg, 1.0))
+        pulled = np.zeros(n, dtype=np.float64)
+        if len(src):
+            np.add.at(pulled, dst, contrib[src])
+        new = teleport + damping * pulled + damping * rank[dangling_nodes].sum() / n
+        change = np.abs(new - rank).sum()
+        rank = new
+        if change < PAGERANK_TOLERANCE:
+            break
+    return rank
+
+
+def _expand_rows(row_off, rows):
+    """(slot index, owning row) for every CSR slot of ``rows``, row by row."""
+    beg = row_off[rows]
+    cnt = row_off[rows + 1] - beg
+    total = int(cnt.sum())
+    if total == 0:
+        empty = np.zeros(0, dtype=np.int64)
+        return empty, empty
+    ends = np.cumsum(cnt)
+    within = np.arange(total, dtype=np.int64) - np.repeat(ends - cnt, cnt)
+    return np.repeat(beg, cnt) + within, np.repeat(rows, cnt)
+
+
+def betweenness(fwd_off, fwd_col, num_nodes: int, sources,
+                etype: Optional[np.ndarray] = None, allowed_mask: int = 0xFFFFFFFF):
+    """Un-normalised Brandes betweenness (unweighted) over the forward CSR;
+    fp64 [N].  Level-synchronous per source: sigma flows down the BFS levels,
+    delta back up, and every reached node except the source adds its delta.
+    Parallel edges count once each; ``etype``/``allowed_mask`` filter edges as
+    in :func:`bfs`.
+    """
+    n = int(num_nodes)
+    bc = np.zeros(n, dtype=np.float64)
+    off = np.asarray(fwd_off, dtype=np.int64)
+    col = np.asarray(fwd_col, dtype=np.int64)
+    keep = None
+    if etype is not None:
+        keep = ((np.uint32(allowed_mask) >> np.asarray(etype, dtype=np.uint32)) & 1).astype(bool)
+    for s in np.asarray(sources, dtype=np.int64):
+        dist = np.full(n, -1, dtype=np.int64)
+        sigma = np.zeros(n, dtype=np.float64)
+        dist[s], sigma[s] = 0, 1.0
+        frontier = np.array([s], dtype=np.int64)
+        dag = []  # per level: (u, w) edges with dist[w] == dist[u] + 1
+        level = 0
+        while len(frontier):
+            level += 1
+            slots, u = _expand_rows(off, frontier)
+            if keep is not None:
+                sel = keep[slots]
+                slots, u = slots[sel], u[sel]
+            w = col[slots]
+            fresh = np.unique(w[dist[w] < 0])
+            dist[fresh] = level
+            down = dist[w] == level
+            u, w = u[down], w[down]
+            np.add.at(sigma, w, sigma[u])
+            dag.append((u, w))
+            frontier = fresh
+        delta = np.zeros(n, dtype=np.float64)
+        for u, w in reversed(dag):
+            np.add.at(delta, u, sigma[u] / sigma[w] * (1.0 + delta[w]))
+        reached = dist >= 0
+        reached[s] = False
+        bc[reached] += delta[reached]
+    return bc

@@ -93,6 +93,22 @@ int abom_rank_order(
     const void* scores, long long n, void* hist, void* bin_scratch, int nblocks,
     void* order, void* stream);
 
+// centrality.hip (abom_pagerank_run returns the number of passes run,
+// abom_brandes_run the deepest BFS level, or a negated hipError_t; the edge
+// types and the heavy-row lists are nullable)
+int abom_pagerank_run(
+    const void* rev_off, const void* rev_col, const void* rev_heavy, long long num_rev_heavy,
+    const void* out_degree, long long num_nodes, double damping, double tolerance,
+    int iterations, void* rank_a, void* rank_b, void* contrib_a, void* contrib_b,
+    void* partials, void* scalars, void* stream);
+int abom_brandes_run(
+    const void* fwd_off, const void* fwd_col, const void* fwd_et,
+    const void* rev_off, const void* rev_col, const void* rev_et, unsigned int allowed_mask,
+    const void* fwd_heavy, long long num_fwd_heavy,
+    const void* rev_heavy, long long num_rev_heavy,
+    const void* sources, int batch, long long num_nodes,
+    void* dist, void* sigma, void* delta, void* bc, void* counter, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

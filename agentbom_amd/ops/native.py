@@ -103,10 +103,35 @@ _SIGNATURES = {
         _c, _i64, _c, _c, _i32,  # scores, n, hist, bin_scratch, nblocks
         _c, _c,                  # order, stream
     ], _i32),
+    "abom_pagerank_run": ([
+        _c, _c, _c, _i64,      # rev_off, rev_col, rev_heavy, num_rev_heavy
+        _c, _i64, _f64, _f64,  # out_degree, num_nodes, damping, tolerance
+        _i32, _c, _c, _c, _c,  # iterations, rank_a, rank_b, contrib_a, contrib_b
+        _c, _c, _c,            # partials, scalars, stream
+    ], _i32),
+    "abom_brandes_run": ([
+        _c, _c, _c,            # fwd_off, fwd_col, fwd_et
+        _c, _c, _c, _u32,      # rev_off, rev_col, rev_et, allowed_mask
+        _c, _i64,              # fwd_heavy, num_fwd_heavy
+        _c, _i64,              # rev_heavy, num_rev_heavy
+        _c, _i32, _i64,        # sources, batch, num_nodes
+        _c, _c, _c, _c, _c, _c,  # dist, sigma, delta, bc, counter, stream
+    ], _i32),
 }
 
 # Byte offsets into the BFS ``counters`` buffer (u32 slots of csrc/bfs.hip)
 _CTR_NEXT, _CTR_HEAVY, _CTR_DEGREE = 0, 4, 8
+
+# Rows with at least this many scanned edges get one wave instead of one
+# thread in the centrality kernels (CENTRALITY_HEAVY_DEGREE, csrc/centrality.hip)
+CENTRALITY_HEAVY_DEGREE = 64
+# PageRank stops after the first pass whose L1 change is below this
+PAGERANK_TOLERANCE = 1e-10
+# Block partial pairs of the PageRank reduction: both grids are capped at 2048
+_PAGERANK_PARTIALS = 2 * 2048
+# Bytes of per-source Brandes state per node: dist u32 + sigma f64 + delta f64
+_BRANDES_CELL_BYTES = 20
+_BRANDES_MAX_BATCH = 64
 
 
 class NativeUnavailable(RuntimeError):
@@ -558,3 +583,114 @@ def rank_bucket_order(scores, workspace: Optional[dict] = None):
                              nblocks, _ptr(order), _stream())
     _check(rc, "abom_rank_order")
     return order
+
+
+# ── Centrality (ops/csrc/centrality.hip) ───────────────────────────────────
+
+
+def _heavy_rows(row_off):
+    """Ids of the rows with >= CENTRALITY_HEAVY_DEGREE edges (int32, ascending):
+    the rows the centrality kernels hand to one wave each."""
+    import torch
+
+    deg = row_off[1:] - row_off[:-1]
+    return torch.nonzero(deg >= CENTRALITY_HEAVY_DEGREE).flatten().to(torch.int32)
+
+
+def pagerank(rev_off, rev_col, out_degree, num_nodes: int, damping: float = 0.85,
+             iterations: int = 50, workspace: Optional[dict] = None):
+    """PageRank by pull power iteration over the reverse CSR; fp64 [N].
+
+    ``rev_off`` int64 [N+1], ``rev_col`` int32 [E] (in-neighbours per node),
+    ``out_degree`` int32 [N].  Dangling mass is spread uniformly.  Stops after
+    ``iterations`` passes or after the first pass whose L1 change is below
+    PAGERANK_TOLERANCE.  Bit-reproducible: no floating-point atomics.
+    """
+    import torch
+
+    lib = load()
+    dev = rev_off.device
+    if num_nodes == 0:
+        return torch.empty(0, dtype=torch.float64, device=dev)
+    ws = workspace if workspace is not None else {}
+    rank_a = _buf(ws, "pr_rank_a", num_nodes, torch.float64, dev)
+    rank_b = _buf(ws, "pr_rank_b", num_nodes, torch.float64, dev)
+    contrib_a = _buf(ws, "pr_contrib_a", num_nodes, torch.float64, dev)
+    contrib_b = _buf(ws, "pr_contrib_b", num_nodes, torch.float64, dev)
+    partials = _buf(ws, "pr_partials", 2 * _PAGERANK_PARTIALS, torch.float64, dev)
+    scalars = _buf(ws, "pr_scalars", 2, torch.float64, dev)
+    heavy = _heavy_rows(rev_off)
+    rc = lib.abom_pagerank_run(
+        _ptr(rev_off), _ptr(rev_col), _ptr(heavy), heavy.numel(),
+        _ptr(out_degree), num_nodes, float(damping), PAGERANK_TOLERANCE,
+        int(iterations), _ptr(rank_a), _ptr(rank_b), _ptr(contrib_a), _ptr(contrib_b),
+        _ptr(partials), _ptr(scalars), _stream(),
+    )
+    if rc < 0:
+        _check(-rc, "abom_pagerank_run")
+    ws["pr_iterations"] = rc  # passes actually run (early stop below the tolerance)
+    # the loop ping-pongs: an even number of passes ends in rank_a
+    return (rank_a if rc % 2 == 0 else rank_b)[:num_nodes].clone()
+
+
+def brandes_batch_size(num_sources: int, num_nodes: int) -> int:
+    """Default Brandes batch: as many sources as fit the workspace budget
+    ($AGENT_BOM_CENTRALITY_WS_MB), at most 64, at least 1."""
+    from agentbom_amd.utils import config as cfg
+
+    budget = cfg.CENTRALITY_WS_MB << 20
+    fit = budget // (_BRANDES_CELL_BYTES * max(num_nodes, 1))
+    return max(1, min(num_sources, _BRANDES_MAX_BATCH, fit))
+
+
+def betweenness(fwd: dict, rev: dict, num_nodes: int, sources, batch: Optional[int] = None,
+                workspace: Optional[dict] = None, allowed_mask: Optional[int] = None):
+    """Un-normalised Brandes betweenness (unweighted) from ``sources``; fp64 [N].
+
+    ``fwd`` / ``rev`` are CSR dicts (``row_off`` int64 [N+1], ``col`` int32
+    [E], optional ``etype`` uint8 [E]).  Sources run ``batch`` at a time with
+    [batch, N] dist/sigma/delta workspaces; the result does not depend on the
+    batch size, bit for bit.  ``workspace["bc_deepest"]`` is left holding the
+    deepest BFS level any source reached.  ``allowed_mask`` filters edges by type bit (needs
+    ``etype`` in both dicts); None walks every edge.
+    """
+    import torch
+
+    lib = load()
+    dev = fwd["row_off"].device
+    bc = torch.zeros(num_nodes, dtype=torch.float64, device=dev)
+    src = np.asarray(sources.cpu() if hasattr(sources, "cpu") else sources, dtype=np.int64)
+    if num_nodes == 0 or src.size == 0:
+        return bc
+    if src.min() < 0 or src.max() >= num_nodes:
+        raise ValueError("betweenness: source id outside [0, num_nodes)")
+    if batch is None:
+        batch = brandes_batch_size(int(src.size), num_nodes)
+    batch = max(1, min(int(batch), int(src.size), 65535))
+    fwd_et = rev_et = None
+    mask = 0xFFFFFFFF
+    if allowed_mask is not None:
+        fwd_et, rev_et, mask = _ptr(fwd["etype"]), _ptr(rev["etype"]), int(allowed_mask)
+    ws = workspace if workspace is not None else {}
+    cells = batch * num_nodes
+    dist = _buf(ws, "bc_dist", cells, torch.int32, dev)
+    sigma = _buf(ws, "bc_sigma", cells, torch.float64, dev)
+    delta = _buf(ws, "bc_delta", cells, torch.float64, dev)
+    counter = _buf(ws, "bc_counter", 1, torch.int32, dev, zero=True)
+    fwd_heavy = _heavy_rows(fwd["row_off"])
+    rev_heavy = _heavy_rows(rev["row_off"])
+    src_dev = torch.from_numpy(src.astype(np.int32)).to(dev)
+    for lo in range(0, int(src.size), batch):
+        chunk = src_dev[lo:lo + batch]
+        rc = lib.abom_brandes_run(
+            _ptr(fwd["row_off"]), _ptr(fwd["col"]), fwd_et,
+            _ptr(rev["row_off"]), _ptr(rev["col"]), rev_et, mask,
+            _ptr(fwd_heavy), fwd_heavy.numel(),
+            _ptr(rev_heavy), rev_heavy.numel(),
+            _ptr(chunk), chunk.numel(), num_nodes,
+            _ptr(dist), _ptr(sigma), _ptr(delta), _ptr(bc), _ptr(counter), _stream(),
+        )
+        if rc < 0:
+            _check(-rc, "abom_brandes_run")
+        ws["bc_deepest"] = max(rc, ws.get("bc_deepest", 0) if lo else 0)
+    return bc

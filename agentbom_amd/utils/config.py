@@ -166,6 +166,9 @@ PATH_MAX_PATHS = _int("AGENT_BOM_PATH_MAX_PATHS", 100)
 BLAST_RADIUS_MAX_DEPTH = _int("AGENT_BOM_BLAST_RADIUS_MAX_DEPTH", 5)
 IMPACT_QUERY_MAX_NODES = _int("AGENT_BOM_IMPACT_QUERY_MAX_NODES", 4096)
 ROLLUP_MAX_CONTAINERS = _int("AGENT_BOM_ROLLUP_MAX_CONTAINERS", 200)
+# Device workspace budget (MiB) for batched Brandes betweenness: the batch is
+# the number of sources whose [N] dist/sigma/delta arrays (20 B/node) fit.
+CENTRALITY_WS_MB = _int("AGENT_BOM_CENTRALITY_WS_MB", 4096)
 
 # ── Transitive expansion / registries ───────────────────────────────────────
 TRANSITIVE_MAX_DEPTH = _int("AGENT_BOM_TRANSITIVE_MAX_DEPTH", 3)
