@@ -81,6 +81,18 @@ def _precompute_win_ranges(torch, arena: dict, pkg_group_key_sorted):
     return wbeg.contiguous(), wend.contiguous()
 
 
+def row_of_from_runs(torch, run_off, perm2):
+    """int32 [P]: package index -> the run (unique row) that holds it, i.e.
+    ``row_of[perm2[k]] == r`` for every k in ``run_off[r]:run_off[r+1]``."""
+    U = run_off.numel() - 1
+    rows = torch.repeat_interleave(
+        torch.arange(U, dtype=torch.int32, device=perm2.device),
+        run_off[1:] - run_off[:-1])
+    row_of = torch.empty(perm2.numel(), dtype=torch.int32, device=perm2.device)
+    row_of[perm2] = rows
+    return row_of
+
+
 def build_dedup_match_layout(torch, arena: dict, gk, hi, lo, flags):
     """Dedup (group, version, flags) rows for the resident-estate match.
 
@@ -93,6 +105,8 @@ def build_dedup_match_layout(torch, arena: dict, gk, hi, lo, flags):
       run_off   int64 [U+1]: unique row -> its span in ``perm2``
       perm2     int64 [P]: sorted-row -> original package index
       u_ranges  precomputed window ranges for the unique rows
+      row_of    int32 [P]: original package index -> its unique row (the
+                inverse of perm2/run_off; read by ops/csrc/findings.hip)
     """
     P = gk.numel()
     # lexicographic stable sort by (gk, hi, lo, flags)
@@ -117,6 +131,7 @@ def build_dedup_match_layout(torch, arena: dict, gk, hi, lo, flags):
         "u_flags": f2[starts].contiguous(),
         "run_off": run_off,
         "perm2": idx,
+        "row_of": row_of_from_runs(torch, run_off, idx),
     }
     layout["u_ranges"] = _precompute_win_ranges(torch, arena, layout["u_gk"])
     # Match schedule experiments (AGENT_BOM_MATCH_SCHEDULE):
@@ -163,9 +178,24 @@ def build_dedup_match_layout(torch, arena: dict, gk, hi, lo, flags):
     return layout
 
 
+def findings_native_enabled() -> bool:
+    """A/B toggle: AGENT_BOM_FINDINGS_NATIVE=0 makes the GPU dedup path of
+    ``EstateEngine.step`` assemble findings with the torch op chain
+    (``expand_dedup_matches`` + ``unique_consecutive`` + ``searchsorted``)
+    instead of ops/csrc/findings.hip."""
+    import os
+
+    return os.environ.get("AGENT_BOM_FINDINGS_NATIVE", "1") != "0"
+
+
 def expand_dedup_matches(torch, layout: dict, su, sw):
     """Fan unique-row matches back out to per-package (orig_idx, win) pairs,
     sorted by (pkg << 32 | win) — identical to the non-dedup output.
+
+    The torch reference of the finding assembly: the single-GPU step runs
+    ops/csrc/findings.hip instead (no sort); this chain remains the oracle
+    of its tests, the AGENT_BOM_FINDINGS_NATIVE=0 path and what the
+    distributed engine and scripts/stage_timing.py call.
 
     Accepts UNSORTED (su, sw) — the one F-sized value sort at the end
     canonicalizes, so match_finalize can skip its pair sort (sort=False).
@@ -274,6 +304,7 @@ class EstateEngine:
 
         self.agent_ids = torch.arange(estate.n_agents, dtype=torch.int32, device=dev)
         self._bfs_ws: dict = {}
+        self._findings_ws: dict = {}  # ops/csrc/findings.hip workspace
         self._match_stream = None  # side stream: match ∥ reach BFS overlap
 
         # per-node db-credential / db-tool indicator (for impact filtering)
@@ -420,12 +451,16 @@ class EstateEngine:
             return self._blast_counts_fused(uniq_pkgs)
         return self._blast_counts_join(uniq_pkgs)
 
-    def _blast_counts_fused(self, uniq_pkgs):
+    def _blast_counts_fused(self, uniq_pkgs, uniq_pkgs32=None):
+        """``uniq_pkgs32``: the same ids as int32, when the caller already
+        has them (the native finding assembly writes both)."""
         from agentbom_amd.ops import native
 
         torch = self.torch
+        if uniq_pkgs32 is None:
+            uniq_pkgs32 = uniq_pkgs.to(torch.int32).contiguous()
         counts, overflow = native.blast_counts(
-            uniq_pkgs.to(torch.int32).contiguous(), self.rev, self.fwd,
+            uniq_pkgs32, self.rev, self.fwd,
             (ET_CONTAINS, ET_USES, ET_HAS_CRED, ET_PROVIDES_TOOL),
             self.node_is_db_cred, self.node_is_db_tool,
         )
@@ -491,6 +526,7 @@ class EstateEngine:
         distances (multi-GPU mode passes the shard's slice of the
         distributed BFS result)."""
         torch = self.torch
+        assembled = None
         if self.use_gpu:
             # Overlap: the match kernel has no dependency on the reach BFS,
             # so it runs on a side HIP stream while the BFS host loop (which
@@ -519,22 +555,33 @@ class EstateEngine:
                         self.arena["windows"], pkg_win_range=self.pkg_win_range)
             dist = reach_dist if reach_dist is not None else self.dependency_reach()
             torch.cuda.current_stream().wait_stream(side)
-            # downstream always re-canonicalizes; skip the pair sort
-            sp, sw = native.match_finalize(pending, sort=False)
-            if dd is not None:
-                pkg_idx, win_idx = expand_dedup_matches(torch, dd, sp, sw)
+            if dd is not None and findings_native_enabled():
+                # pairs -> sorted findings + unique packages + positions in
+                # HIP (ops/csrc/findings.hip): no sort, one host read
+                assembled = native.assemble_findings(
+                    pending, dd, self.estate.pkg_base, self._findings_ws)
             else:
-                pkg_idx, win_idx = self._unsort_matches(sp, sw)
+                # downstream always re-canonicalizes; skip the pair sort
+                sp, sw = native.match_finalize(pending, sort=False)
+                if dd is not None:
+                    pkg_idx, win_idx = expand_dedup_matches(torch, dd, sp, sw)
+                else:
+                    pkg_idx, win_idx = self._unsort_matches(sp, sw)
         else:
             pkg_idx, win_idx = self.match()
             dist = reach_dist if reach_dist is not None else self.dependency_reach()
+
+        if assembled is not None:
+            pkg_idx, win_idx = assembled["pkg_idx"], assembled["win_idx"]
+            pkg_nodes, pos = assembled["pkg_nodes"], assembled["pos"]
+            counts = self._blast_counts_fused(assembled["uniq_pkgs"],
+                                              assembled["uniq_pkgs32"])
+        else:
+            pkg_nodes = pkg_idx + self.estate.pkg_base
+            counts = self.blast_counts(pkg_nodes)
+            # map each finding to its unique-package position
+            pos = torch.searchsorted(counts["uniq_pkgs"], pkg_nodes)
         n_findings = pkg_idx.numel()
-
-        pkg_nodes = pkg_idx + self.estate.pkg_base
-        counts = self.blast_counts(pkg_nodes)
-
-        # map each finding to its unique-package position
-        pos = torch.searchsorted(counts["uniq_pkgs"], pkg_nodes)
 
         if self.use_gpu:
             # fused gather + score: arena gathers, CWE-impact LUT count

@@ -93,6 +93,24 @@ int abom_rank_order(
     const void* scores, long long n, void* hist, void* bin_scratch, int nblocks,
     void* order, void* stream);
 
+// findings.hip (abom_findings_count leaves {findings, unique packages, match
+// count} in totals; the caller reads them, sizes the outputs and calls
+// abom_findings_emit, which also returns the workspace to all-zero)
+int abom_findings_count(
+    const void* pairs, const void* count, long long capacity,
+    const void* run_off, const void* perm2, const void* row_of,
+    long long num_rows, long long num_packages,
+    void* bitmap, void* row_cnt, void* row_tail, void* chain_prev,
+    void* rank_of, void* word_f, void* block_sums, void* totals, void* stream);
+int abom_findings_emit(
+    const void* pairs, const void* count, long long capacity,
+    const void* row_of, long long num_rows, long long num_packages,
+    void* bitmap, void* row_cnt, void* row_tail, const void* chain_prev,
+    const void* rank_of, const void* word_f, const void* block_off,
+    long long pkg_base, long long num_findings, long long num_unique,
+    void* out_pkg_idx, void* out_win_idx, void* out_pkg_nodes, void* out_pos,
+    void* out_uniq64, void* out_uniq32, void* stream);
+
 // centrality.hip (abom_pagerank_run returns the number of passes run,
 // abom_brandes_run the deepest BFS level, or a negated hipError_t; the edge
 // types and the heavy-row lists are nullable)

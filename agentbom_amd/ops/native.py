@@ -103,6 +103,22 @@ _SIGNATURES = {
         _c, _i64, _c, _c, _i32,  # scores, n, hist, bin_scratch, nblocks
         _c, _c,                  # order, stream
     ], _i32),
+    "abom_findings_count": ([
+        _c, _c, _i64,        # pairs, count, capacity
+        _c, _c, _c,          # run_off, perm2, row_of
+        _i64, _i64,          # num_rows, num_packages
+        _c, _c, _c, _c,      # bitmap, row_cnt, row_tail, chain_prev
+        _c, _c, _c, _c, _c,  # rank_of, word_f, block_sums, totals, stream
+    ], _i32),
+    "abom_findings_emit": ([
+        _c, _c, _i64,     # pairs, count, capacity
+        _c, _i64, _i64,   # row_of, num_rows, num_packages
+        _c, _c, _c, _c,   # bitmap, row_cnt, row_tail, chain_prev
+        _c, _c, _c,       # rank_of, word_f, block_off
+        _i64, _i64, _i64,  # pkg_base, num_findings, num_unique
+        _c, _c, _c, _c,   # out_pkg_idx, out_win_idx, out_pkg_nodes, out_pos
+        _c, _c, _c,       # out_uniq64, out_uniq32, stream
+    ], _i32),
     "abom_pagerank_run": ([
         _c, _c, _c, _i64,      # rev_off, rev_col, rev_heavy, num_rev_heavy
         _c, _i64, _f64, _f64,  # out_degree, num_nodes, damping, tolerance
@@ -283,6 +299,89 @@ def match_finalize(pending: dict, sort: bool = True):
     if sort:
         pairs, _ = torch.sort(pairs)
     return (pairs >> 32).to(torch.int64), (pairs & 0xFFFFFFFF).to(torch.int64)
+
+
+_FINDINGS_BLOCK = 256  # bitmap words per block (FA_BLOCK, csrc/findings.hip)
+
+
+def assemble_findings(pending: dict, layout: dict, pkg_base: int, workspace: dict) -> dict:
+    """Dedup-match pairs -> the canonical finding stream, without a sort.
+
+    Takes the pending handle of a :func:`match_launch` over the DISTINCT rows
+    of ``layout`` (``run_off``, ``perm2``, ``row_of``) and returns, equal to
+    ``expand_dedup_matches`` + ``unique_consecutive`` + ``searchsorted``:
+
+      pkg_idx, win_idx   int64 [F], sorted by (pkg << 32 | win)
+      pkg_nodes          int64 [F] = pkg_idx + pkg_base
+      pos                int64 [F], index of the finding's package in uniq_pkgs
+      uniq_pkgs          int64 [NU], ascending distinct pkg_nodes
+      uniq_pkgs32        int32 [NU], the same (abom_blast_counts input)
+
+    One host read (findings, unique packages, match count) sizes the outputs.
+    On capacity overflow the match is relaunched with a grown buffer, as in
+    :func:`match_finalize`.  ``workspace`` persists between calls and is
+    all-zero outside a call; a call that did not finish leaves it flagged and
+    the next call clears it in full.
+    """
+    import torch
+
+    lib = load()
+    pairs, count = pending["out_pairs"], pending["out_count"]
+    cap = min(int(pending["cap"]), pairs.numel())
+    dev = pairs.device
+    run_off, perm2, row_of = layout["run_off"], layout["perm2"], layout["row_of"]
+    U, P = run_off.numel() - 1, perm2.numel()
+    if P == 0 or cap == 0:
+        e64 = [torch.empty(0, dtype=torch.int64, device=dev) for _ in range(5)]
+        return dict(zip(("pkg_idx", "win_idx", "pkg_nodes", "pos", "uniq_pkgs"), e64),
+                    uniq_pkgs32=torch.empty(0, dtype=torch.int32, device=dev))
+    ws = workspace
+    W = (P + 63) // 64
+    nblocks = (W + _FINDINGS_BLOCK - 1) // _FINDINGS_BLOCK
+    bitmap = _buf(ws, "fa_bitmap", W, torch.int64, dev, zero=True)
+    row_cnt = _buf(ws, "fa_row_cnt", U, torch.int32, dev, zero=True)
+    row_tail = _buf(ws, "fa_row_tail", U, torch.int32, dev, zero=True)
+    chain_prev = _buf(ws, "fa_chain_prev", cap, torch.int32, dev)
+    rank_of = _buf(ws, "fa_rank_of", cap, torch.int32, dev)
+    word_f = _buf(ws, "fa_word_f", W, torch.int32, dev)
+    block_sums = _buf(ws, "fa_block_sums", 2 * nblocks, torch.int64, dev)
+    totals = _buf(ws, "fa_totals", 3, torch.int64, dev)
+    if ws.get("fa_dirty"):
+        bitmap.zero_()
+        row_cnt.zero_()
+        row_tail.zero_()
+    ws["fa_dirty"] = True
+    rc = lib.abom_findings_count(
+        _ptr(pairs), _ptr(count), cap, _ptr(run_off), _ptr(perm2), _ptr(row_of), U, P,
+        _ptr(bitmap), _ptr(row_cnt), _ptr(row_tail), _ptr(chain_prev),
+        _ptr(rank_of), _ptr(word_f), _ptr(block_sums), _ptr(totals), _stream(),
+    )
+    _check(rc, "abom_findings_count")
+    F, NU, n = totals.tolist()  # the one host sync of the assembly
+    if n < 0:
+        raise RuntimeError("match: device match count overflowed int32; shard the package batch")
+    if n > cap:
+        relaunched = match_launch(*pending["args"], capacity=int(n * 1.2) + 1024,
+                                  **pending.get("kw", {}))
+        return assemble_findings(relaunched, layout, pkg_base, ws)
+    if F >= 1 << 31:
+        raise RuntimeError(f"assemble_findings: {F} findings exceed int32; shard the package batch")
+    pkg_idx, win_idx, pkg_nodes, pos = (
+        torch.empty(F, dtype=torch.int64, device=dev) for _ in range(4))
+    uniq64 = torch.empty(NU, dtype=torch.int64, device=dev)
+    uniq32 = torch.empty(NU, dtype=torch.int32, device=dev)
+    rc = lib.abom_findings_emit(
+        _ptr(pairs), _ptr(count), cap, _ptr(row_of), U, P,
+        _ptr(bitmap), _ptr(row_cnt), _ptr(row_tail), _ptr(chain_prev),
+        _ptr(rank_of), _ptr(word_f), _ptr(block_sums),
+        int(pkg_base), F, NU,
+        _ptr(pkg_idx), _ptr(win_idx), _ptr(pkg_nodes), _ptr(pos),
+        _ptr(uniq64), _ptr(uniq32), _stream(),
+    )
+    _check(rc, "abom_findings_emit")
+    ws["fa_dirty"] = False
+    return {"pkg_idx": pkg_idx, "win_idx": win_idx, "pkg_nodes": pkg_nodes, "pos": pos,
+            "uniq_pkgs": uniq64, "uniq_pkgs32": uniq32}
 
 
 def match(pkg_group_key, pkg_key_hi, pkg_key_lo, pkg_flags, group_keys, group_off,
