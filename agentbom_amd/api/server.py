@@ -599,6 +599,23 @@ def create_app() -> FastAPI:
         return {"metric": metric,
                 "centrality": [{"id": nid, "score": score} for nid, score in top]}
 
+    @app.get("/v1/graph/components", dependencies=[Depends(auth)])
+    def graph_components(
+            request: Request, top_n: int = 20,
+            view: Literal["lateral", "all"] = "lateral",
+            backend: Optional[str] = None) -> dict:
+        """Segmentation: lateral-movement domains (agents tied together by
+        shared servers and credentials), or with view=all the connected
+        components over every edge, largest first."""
+        g = _latest_graph(request)
+        if view == "lateral":
+            return {"view": view, "domains": g.lateral_domains(top_n, backend=backend)}
+        domains = g.component_domains(g.connected_components(backend=backend))
+        domains.sort(key=lambda d: (-d["size"], d["id"]))
+        return {"view": view, "components": len(domains),
+                "largest": domains[0]["size"] if domains else 0,
+                "domains": domains[:top_n]}
+
     @app.get("/v1/graph/bottlenecks", dependencies=[Depends(auth)])
     def graph_bottlenecks(request: Request, top_n: int = 10, sample: int = 64,
                           method: Literal["approx", "brandes"] = "approx",

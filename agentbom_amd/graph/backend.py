@@ -1,4 +1,5 @@
-"""Graph-analytics backend protocol: PageRank + betweenness centrality.
+"""Graph-analytics backend protocol: PageRank, betweenness centrality and
+connected components.
 
 Reference parity: src/agent_bom/graph_backend.py:25 — an optional analytics
 backend behind a Protocol, NetworkX when installed, with the container's
@@ -6,9 +7,9 @@ built-in approximations otherwise.  MI355X build ships a NATIVE numpy
 backend as the default (power-iteration PageRank, Brandes betweenness on a
 bounded sample) so the analytics work in the air-gapped image where
 networkx is absent; the NetworkX adapter remains for environments that
-have it (``AGENT_BOM_GRAPH_BACKEND=networkx``).  ``hip`` runs the same two
-analytics as HIP kernels (ops/csrc/centrality.hip) where a GPU and the built
-engine are present.
+have it (``AGENT_BOM_GRAPH_BACKEND=networkx``).  ``hip`` runs the same
+analytics as HIP kernels (ops/csrc/centrality.hip, ops/csrc/components.hip)
+where a GPU and the built engine are present.
 """
 
 from __future__ import annotations
@@ -29,6 +30,8 @@ class GraphBackendProtocol(Protocol):
                  iterations: int = 50) -> dict[str, float]: ...
 
     def betweenness(self, graph, sample: int = 64) -> dict[str, float]: ...
+
+    def components(self, graph, relationships=None) -> dict[str, str]: ...
 
 
 class NativeBackend:
@@ -121,6 +124,16 @@ class NativeBackend:
                 scores[k] /= norm
         return scores
 
+    def components(self, graph, relationships=None) -> dict[str, str]:
+        """Node id -> the lexicographically smallest id of its weakly
+        connected component, over every edge (undirected) or only those of
+        the given ``RelationshipType``s."""
+        from agentbom_amd.ops import cpu_ref
+
+        ids, src, dst = component_edges(graph, relationships)
+        labels = cpu_ref.connected_components(src, dst, len(ids))
+        return {nid: ids[labels[i]] for i, nid in enumerate(ids)}
+
 
 class NetworkXBackend:
     """Adapter for environments that have networkx installed."""
@@ -152,6 +165,16 @@ class NetworkXBackend:
         k = min(sample, g.number_of_nodes()) or None
         return dict(self._nx.betweenness_centrality(g, k=k, seed=7))
 
+    def components(self, graph, relationships=None) -> dict[str, str]:
+        ids, src, dst = component_edges(graph, relationships)
+        g = self._nx.Graph()
+        g.add_nodes_from(ids)
+        g.add_edges_from((ids[u], ids[v]) for u, v in zip(src.tolist(), dst.tolist()))
+        out = {}
+        for members in self._nx.connected_components(g):
+            out.update(dict.fromkeys(members, min(members)))
+        return {nid: out[nid] for nid in ids}
+
 
 def brandes_sources(n: int, sample: int) -> range:
     """NativeBackend's deterministic source sample: every node when
@@ -177,6 +200,22 @@ def traversable_edges(graph) -> tuple[list[str], np.ndarray, np.ndarray]:
             np.asarray(dst_idx, dtype=np.int64))
 
 
+def component_edges(graph, relationships=None) -> tuple[list[str], np.ndarray, np.ndarray]:
+    """(ids, src, dst) for the component analytics: nodes in sorted-id order
+    (so the smallest index of a component is its smallest id), every edge
+    once whatever its direction or traversability, restricted to
+    ``relationships`` when given; int32 index arrays."""
+    ids, pos = NativeBackend._index(graph)
+    keep = None if relationships is None else set(relationships)
+    src_idx, dst_idx = [], []
+    for e in graph.edges:
+        if keep is None or e.relationship in keep:
+            src_idx.append(pos[e.source])
+            dst_idx.append(pos[e.target])
+    return (ids, np.asarray(src_idx, dtype=np.int32),
+            np.asarray(dst_idx, dtype=np.int32))
+
+
 def csr_arrays(rows: np.ndarray, cols: np.ndarray, n: int) -> tuple[np.ndarray, np.ndarray]:
     """(row_off int64 [n+1], col int32 [E]) of the edges rows -> cols; the
     edges of one row keep their input order."""
@@ -187,8 +226,9 @@ def csr_arrays(rows: np.ndarray, cols: np.ndarray, n: int) -> tuple[np.ndarray, 
 
 
 class HipBackend:
-    """The NativeBackend analytics on the GPU (ops/csrc/centrality.hip), with
-    the same index, edge set and result contracts (traversable_edges)."""
+    """The NativeBackend analytics on the GPU (ops/csrc/centrality.hip,
+    ops/csrc/components.hip), with the same index, edge set and result
+    contracts (traversable_edges, component_edges)."""
 
     name = "hip"
 
@@ -230,6 +270,20 @@ class HipBackend:
         bc = native.betweenness(fwd, rev, n, brandes_sources(n, sample)).cpu().numpy()
         bc = bc / ((n - 1) * (n - 2))
         return {nid: float(bc[i]) for i, nid in enumerate(ids)}
+
+    def components(self, graph, relationships=None) -> dict[str, str]:
+        import torch
+
+        from agentbom_amd.ops import native
+
+        ids, src, dst = component_edges(graph, relationships)
+        if not ids:
+            return {}
+        dev = torch.device("cuda")
+        labels = native.connected_components(
+            torch.from_numpy(src).to(dev), torch.from_numpy(dst).to(dev),
+            len(ids)).cpu().numpy()
+        return {nid: ids[labels[i]] for i, nid in enumerate(ids)}
 
 
 def _hip_usable() -> bool:

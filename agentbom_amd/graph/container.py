@@ -24,6 +24,17 @@ from agentbom_amd.graph.types import EntityType, GraphSemanticLayer, NodeStatus,
 DEFAULT_NODE_BUDGET = 250_000
 IMPACT_MAX_HOPS = 4
 
+# The relationships of view("lateral"); lateral_domains() adds the two
+# inventory relationships that tie agents to servers and servers to credentials.
+LATERAL_RELATIONSHIPS = frozenset({
+    RelationshipType.SHARES_SERVER, RelationshipType.SHARES_CRED,
+    RelationshipType.LATERAL_PATH, RelationshipType.DELEGATED_TO,
+})
+LATERAL_DOMAIN_RELATIONSHIPS = LATERAL_RELATIONSHIPS | {
+    RelationshipType.USES, RelationshipType.EXPOSES_CRED,
+}
+DOMAIN_MEMBER_LIMIT = 25
+
 
 @dataclass
 class UnifiedNode:
@@ -367,6 +378,47 @@ class UnifiedGraph:
         ranked = sorted(counts.items(), key=lambda kv: (-kv[1], kv[0]))[:top_n]
         return [(n, c / total) for n, c in ranked]
 
+    def connected_components(self, relationships: Optional[Iterable[RelationshipType]] = None,
+                             backend: Optional[str] = None) -> dict[str, str]:
+        """Node id -> the smallest id of its weakly connected component,
+        through the analytics backend.  Every edge counts, in both
+        directions; ``relationships`` restricts the edge set."""
+        from agentbom_amd.graph.backend import get_backend
+
+        return get_backend(backend).components(self, relationships=relationships)
+
+    def component_domains(self, labels: dict[str, str]) -> list[dict[str, Any]]:
+        """One dict per component of ``labels`` (a connected_components()
+        result): ``{"id", "agents", "servers", "credentials", "size",
+        "members"}``, members being the first 25 ids in sorted order.
+        Ordered by ascending id."""
+        groups: dict[str, list[str]] = {}
+        for nid in sorted(labels):
+            groups.setdefault(labels[nid], []).append(nid)
+
+        def count(members: list[str], entity_type: EntityType) -> int:
+            return sum(1 for m in members if self.nodes[m].entity_type == entity_type)
+
+        return [{
+            "id": root,
+            "agents": count(members, EntityType.AGENT),
+            "servers": count(members, EntityType.SERVER),
+            "credentials": count(members, EntityType.CREDENTIAL),
+            "size": len(members),
+            "members": members[:DOMAIN_MEMBER_LIMIT],
+        } for root, members in sorted(groups.items())]
+
+    def lateral_domains(self, top_n: int = 20,
+                        backend: Optional[str] = None) -> list[dict[str, Any]]:
+        """Lateral-movement domains: the components over the lateral view's
+        relationships plus USES and EXPOSES_CRED (agents tied together
+        through shared servers and shared credentials) that hold at least
+        two agents, by descending agent count, then ascending id."""
+        labels = self.connected_components(LATERAL_DOMAIN_RELATIONSHIPS, backend=backend)
+        domains = [d for d in self.component_domains(labels) if d["agents"] >= 2]
+        domains.sort(key=lambda d: (-d["agents"], d["id"]))
+        return domains[:top_n]
+
     # ── typed views (reference container.py:956-1015) ─────────────────────
 
     _VIEW_FILTERS: dict[str, Callable] = {}
@@ -383,8 +435,7 @@ class UnifiedGraph:
                         RelationshipType.REACHES_TOOL, RelationshipType.EXPOSED_TO,
                         RelationshipType.CAN_ACCESS}
         elif name == "lateral":
-            keep_rel = {RelationshipType.SHARES_SERVER, RelationshipType.SHARES_CRED,
-                        RelationshipType.LATERAL_PATH, RelationshipType.DELEGATED_TO}
+            keep_rel = set(LATERAL_RELATIONSHIPS)
         elif name == "runtime":
             keep_rel = {RelationshipType.INVOKED, RelationshipType.CALLED,
                         RelationshipType.USED_CREDENTIAL, RelationshipType.ACCESSED,

@@ -15,6 +15,8 @@ construction) and stays resident in HBM3E.  On top of it:
                          the /v1/graph read path
 - ``pagerank()`` / ``betweenness()`` / ``choke_points()`` centrality on
                          the resident CSR (ops/csrc/centrality.hip)
+- ``components()`` / ``lateral_domains()`` connected components and the
+                         per-domain findings roll-up (ops/csrc/components.hip)
 
 Replaces the reference's scan_packages hot loop + graph dict walks
 (reference: src/agent_bom/scanners/package_scan.py:1307-2028,
@@ -969,6 +971,109 @@ class EstateEngine:
                 etype=self.fwd["etype"].numpy() if masked else None,
                 allowed_mask=allowed_mask if masked else 0xFFFFFFFF))
         return bc / float((n - 1) * (n - 2))
+
+    # ── segmentation on the resident estate (ops/csrc/components.hip) ──────
+
+    # node classes of lateral_domains, in estate id-range order
+    KIND_AGENT, KIND_SERVER, KIND_CRED, KIND_TOOL, KIND_PACKAGE = range(5)
+
+    def components(self, allowed_mask: Optional[int] = None):
+        """Weakly connected components of the estate; int32 tensor [N] on the
+        engine's device, each node labelled with the smallest node id of its
+        component.  ``allowed_mask`` keeps only the edge types whose bit is
+        set (None joins over every edge); direction is ignored."""
+        masked = allowed_mask is not None
+        if self.use_gpu:
+            from agentbom_amd.ops import native
+
+            return native.connected_components(
+                self.fwd["src"], self.fwd["col"], self.N,
+                etype=self.fwd["etype"] if masked else None,
+                allowed_mask=allowed_mask, workspace=self._centrality_ws())
+        from agentbom_amd.ops import cpu_ref
+
+        return self.torch.from_numpy(cpu_ref.connected_components(
+            self.fwd["src"].numpy(), self.fwd["col"].numpy(), self.N,
+            etype=self.fwd["etype"].numpy() if masked else None,
+            allowed_mask=allowed_mask if masked else 0xFFFFFFFF))
+
+    def _node_kind(self):
+        """uint8 [N]: the KIND_* class of every node, from the id ranges."""
+        kind = getattr(self, "_node_kind_cache", None)
+        if kind is None:
+            est = self.estate
+            bounds = self.torch.tensor(
+                [est.server_base, est.cred_base, est.tool_base, est.pkg_base],
+                device=self.device)
+            kind = self.torch.bucketize(
+                self.torch.arange(self.N, device=self.device), bounds,
+                right=True).to(self.torch.uint8)
+            self._node_kind_cache = kind
+        return kind
+
+    def lateral_domains(self, step_res=None, k: int = 20,
+                        allowed_mask: int = (1 << ET_USES) | (1 << ET_HAS_CRED)):
+        """Lateral-movement domains: the components under ``allowed_mask``
+        (by default agents, servers and credentials tied together through
+        USES and HAS_CRED edges) that contain at least one agent, with their
+        findings rolled up.
+
+        A domain's findings are the sum of ``rollup(step_res)
+        ["server_findings"]`` over its servers and its worst severity the
+        minimum of their ``server_worst`` column (0 = critical .. 6 = none).
+        A package contained by several servers of one domain therefore
+        counts once per server, exactly as in :meth:`rollup`.
+
+        Returns device tensors over the domains, ordered by descending
+        findings, ties by ascending root, truncated to ``k``: ``root`` (the
+        component label), ``agents``, ``servers``, ``creds`` (int32),
+        ``findings`` (int64), ``worst`` (int32); and the scalars
+        ``n_domains`` (before truncation) and ``largest_agents``.
+        """
+        torch = self.torch
+        est = self.estate
+        labels = self.components(allowed_mask)
+        # dense renumbering of the roots, ascending by root id
+        is_root = labels == torch.arange(self.N, dtype=torch.int32, device=self.device)
+        dense = torch.cumsum(is_root, 0, dtype=torch.int32) - 1
+        comp = dense[labels.to(torch.int64)].contiguous()
+        roots = torch.nonzero(is_root).flatten()
+        n_comp = int(roots.numel())
+
+        roll = self.rollup(step_res)
+        servers = slice(est.server_base, est.server_base + est.n_servers)
+        weight = torch.zeros(self.N, dtype=torch.int32, device=self.device)
+        weight[servers] = roll["server_findings"].to(torch.int32)
+        worst = torch.full((self.N,), 6, dtype=torch.uint8, device=self.device)
+        worst[servers] = roll["server_worst"].to(torch.uint8)
+        kind = self._node_kind()
+        if self.use_gpu:
+            from agentbom_amd.ops import native
+
+            kind_counts, findings, worst_min = native.component_stats(
+                comp, kind, n_comp, 5, weight=weight, worst=worst)
+        else:
+            from agentbom_amd.ops import cpu_ref
+
+            kind_counts, findings, worst_min = (torch.from_numpy(a) for a in (
+                cpu_ref.component_stats(comp.numpy(), kind.numpy(), n_comp, 5,
+                                        weight=weight.numpy(), worst=worst.numpy())))
+
+        sel = torch.nonzero(kind_counts[:, self.KIND_AGENT] > 0).flatten()
+        agents = kind_counts[sel, self.KIND_AGENT]
+        # stable: equal findings stay in ascending-root order
+        _neg, order = torch.sort(-findings[sel], stable=True)
+        top = sel[order[:k]]
+        return {
+            "root": roots[top].to(torch.int32),
+            "agents": kind_counts[top, self.KIND_AGENT],
+            "servers": kind_counts[top, self.KIND_SERVER],
+            "creds": kind_counts[top, self.KIND_CRED],
+            "findings": findings[top],
+            "worst": worst_min[top],
+            "n_domains": int(sel.numel()),
+            "largest_agents": int(agents.max().item()) if sel.numel() else 0,
+        }
 
     def choke_points(self, k: int = 20, sample: int = 64):
         """The k nodes most shortest paths funnel through: (node_ids int64 [k],

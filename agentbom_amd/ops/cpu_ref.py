@@ -340,3 +340,61 @@ def betweenness(fwd_off, fwd_col, num_nodes: int, sources,
         reached[s] = False
         bc[reached] += delta[reached]
     return bc
+
+
+# ── connected components (oracle for csrc/components.hip) ───────────────────
+
+
+def connected_components(edge_src, col, num_nodes: int,
+                         etype: Optional[np.ndarray] = None, allowed_mask: int = 0xFFFFFFFF):
+    """Weakly connected components of an edge list; int32 labels [N], each the
+    smallest node id of the node's component (the kernel's contract).
+
+    Min-label propagation to a fixed point: every edge whose endpoints carry
+    different labels pulls the larger label's entry down to the smaller
+    (``np.minimum.at``), then pointer jumping flattens ``labels[labels]``;
+    repeated until no edge disagrees.  ``etype``/``allowed_mask`` filter
+    edges as in :func:`bfs`.
+    """
+    n = int(num_nodes)
+    labels = np.arange(n, dtype=np.int64)
+    u = np.asarray(edge_src, dtype=np.int64)
+    v = np.asarray(col, dtype=np.int64)
+    if etype is not None:
+        keep = ((np.uint32(allowed_mask) >> np.asarray(etype, dtype=np.uint32)) & 1).astype(bool)
+        u, v = u[keep], v[keep]
+    while len(u):
+        lu, lv = labels[u], labels[v]
+        differ = lu != lv
+        if not differ.any():
+            break
+        lo = np.minimum(lu, lv)[differ]
+        hi = np.maximum(lu, lv)[differ]
+        np.minimum.at(labels, hi, lo)
+        while True:
+            jumped = labels[labels]
+            if np.array_equal(jumped, labels):
+                break
+            labels = jumped
+    return labels.astype(np.int32)
+
+
+def component_stats(comp, kind, num_components: int, num_kinds: int,
+                    weight: Optional[np.ndarray] = None, worst: Optional[np.ndarray] = None):
+    """Per-component roll-up, the mirror of abom_component_stats: returns
+    ``(kind_counts int32 [C, num_kinds], weight_sum int64 [C], worst_min
+    int32 [C])``.  ``comp`` is a dense component index per node, ``kind`` the
+    node class, ``weight`` an int32 column summed in 64 bits, ``worst`` a
+    severity column where lower is worse.  Without ``weight`` the sums are 0;
+    without ``worst`` worst_min is -1 (the kernel's 0xFFFFFFFF fill)."""
+    C, K = int(num_components), int(num_kinds)
+    comp = np.asarray(comp, dtype=np.int64)
+    kind_counts = np.bincount(comp * K + np.asarray(kind, dtype=np.int64),
+                              minlength=C * K).astype(np.int32).reshape(C, K)
+    weight_sum = np.zeros(C, dtype=np.int64)
+    if weight is not None:
+        np.add.at(weight_sum, comp, np.asarray(weight, dtype=np.int64))
+    worst_min = np.full(C, 0xFFFFFFFF, dtype=np.uint32)
+    if worst is not None:
+        np.minimum.at(worst_min, comp, np.asarray(worst, dtype=np.uint32))
+    return kind_counts, weight_sum, worst_min.view(np.int32)

@@ -127,6 +127,18 @@ int abom_brandes_run(
     const void* sources, int batch, long long num_nodes,
     void* dist, void* sigma, void* delta, void* bc, void* counter, void* stream);
 
+// components.hip (abom_components_run returns the number of rounds run,
+// max_rounds + 1 when that cap was hit before a round hooked nothing, or a
+// negated hipError_t; etype, weight and worst are nullable)
+int abom_components_run(
+    const void* edge_src, const void* col, const void* etype, unsigned int allowed_mask,
+    long long num_edges, long long num_nodes, void* labels, void* counters,
+    int max_rounds, void* stream);
+int abom_component_stats(
+    const void* comp, const void* kind, const void* weight, const void* worst,
+    long long num_nodes, long long num_components, int num_kinds,
+    void* kind_counts, void* weight_sum, void* worst_min, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,16 @@ _SIGNATURES = {
         _c, _i32, _i64,        # sources, batch, num_nodes
         _c, _c, _c, _c, _c, _c,  # dist, sigma, delta, bc, counter, stream
     ], _i32),
+    "abom_components_run": ([
+        _c, _c, _c, _u32,    # edge_src, col, etype, allowed_mask
+        _i64, _i64, _c, _c,  # num_edges, num_nodes, labels, counters
+        _i32, _c,            # max_rounds, stream
+    ], _i32),
+    "abom_component_stats": ([
+        _c, _c, _c, _c,    # comp, kind, weight, worst
+        _i64, _i64, _i32,  # num_nodes, num_components, num_kinds
+        _c, _c, _c, _c,    # kind_counts, weight_sum, worst_min, stream
+    ], _i32),
 }
 
 # Byte offsets into the BFS ``counters`` buffer (u32 slots of csrc/bfs.hip)
@@ -793,3 +803,126 @@ def betweenness(fwd: dict, rev: dict, num_nodes: int, sources, batch: Optional[i
             _check(-rc, "abom_brandes_run")
         ws["bc_deepest"] = max(rc, ws.get("bc_deepest", 0) if lo else 0)
     return bc
+
+
+# ── Connected components (ops/csrc/components.hip) ─────────────────────────
+
+# component_stats packs one 8-bit counter per node class (CC_MAX_KINDS)
+COMPONENT_MAX_KINDS = 8
+
+
+def _require(t, name: str, dtype, dev, numel: Optional[int] = None) -> None:
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
+    if t.device != dev:
+        raise ValueError(f"{name}: on {t.device}, expected {dev}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: not contiguous")
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f"{name}: {t.numel()} elements, expected {numel}")
+
+
+def components_max_rounds(num_nodes: int) -> int:
+    """Default round cap of :func:`connected_components`: ``num_nodes + 1``.
+
+    A round that hooks anything turns at least one root into a non-root, and
+    a non-root never becomes a root again (csrc/components.hip, header).  N
+    nodes start as N roots and at least one survives, so at most N-1 rounds
+    hook; the round after them hooks nothing and ends the loop.  N rounds
+    therefore always suffice, whatever the schedule, and the one on top keeps
+    the cap itself out of reach: hitting it means the engine is broken, not
+    that the graph was hard.  Real graphs take a handful of rounds.
+    """
+    return min(int(num_nodes) + 1, (1 << 31) - 2)
+
+
+def connected_components(edge_src, col, num_nodes: int, etype=None,
+                         allowed_mask: Optional[int] = None, workspace: Optional[dict] = None,
+                         max_rounds: Optional[int] = None):
+    """Weakly connected components of an edge list; int32 labels [N].
+
+    ``edge_src`` / ``col`` are int32 [E] device tensors (edge e joins
+    ``edge_src[e]`` and ``col[e]``; direction is ignored, self-loops and
+    parallel edges are harmless).  ``labels[v]`` is the smallest node id of
+    v's component, so the result is the same bit for bit on every run.
+    ``allowed_mask`` keeps only the edges whose ``etype`` (uint8 [E]) bit is
+    set; None walks every edge.  Raises if ``max_rounds`` (default
+    :func:`components_max_rounds`) rounds did not reach the fixed point;
+    unconverged labels are never returned.  ``workspace["cc_rounds"]`` is
+    left holding the rounds run.
+    """
+    import torch
+
+    lib = load()
+    num_nodes = int(num_nodes)
+    if not 0 <= num_nodes < 1 << 31:
+        raise ValueError(f"connected_components: num_nodes {num_nodes} outside [0, 2^31)")
+    dev = edge_src.device
+    if dev.type != "cuda":
+        raise ValueError(f"connected_components: edge_src on {dev}, expected a GPU tensor")
+    num_edges = edge_src.numel()
+    _require(edge_src, "edge_src", torch.int32, dev)
+    _require(col, "col", torch.int32, dev, num_edges)
+    et, mask = None, 0xFFFFFFFF
+    if allowed_mask is not None:
+        if etype is None:
+            raise ValueError("connected_components: allowed_mask needs etype")
+        _require(etype, "etype", torch.uint8, dev, num_edges)
+        et, mask = _ptr(etype), int(allowed_mask) & 0xFFFFFFFF
+    if max_rounds is None:
+        max_rounds = components_max_rounds(num_nodes)
+    ws = workspace if workspace is not None else {}
+    labels = torch.empty(num_nodes, dtype=torch.int32, device=dev)
+    counters = _buf(ws, "cc_counters", 1, torch.int32, dev, zero=True)
+    rc = lib.abom_components_run(
+        _ptr(edge_src), _ptr(col), et, mask, num_edges, num_nodes,
+        _ptr(labels), _ptr(counters), int(max_rounds), _stream(),
+    )
+    if rc < 0:
+        _check(-rc, "abom_components_run")
+    if rc > max_rounds:
+        raise RuntimeError(
+            f"connected_components: no fixed point after {max_rounds} rounds")
+    ws["cc_rounds"] = rc
+    return labels
+
+
+def component_stats(comp, kind, num_components: int, num_kinds: int, weight=None, worst=None):
+    """Per-component roll-up of node columns; integer atomics only, so the
+    result is bit-reproducible.
+
+    ``comp`` int32 [N] is a dense component index in [0, num_components),
+    ``kind`` uint8 [N] a node class in [0, num_kinds) (at most 8 classes),
+    ``weight`` int32 [N] and ``worst`` uint8 [N] (lower is worse) are
+    optional.  Returns ``(kind_counts int32 [C, num_kinds], weight_sum int64
+    [C], worst_min int32 [C])``; without ``weight`` the sums are 0, without
+    ``worst`` worst_min is -1 (the u32 fill pattern).
+    """
+    import torch
+
+    lib = load()
+    dev = comp.device
+    if dev.type != "cuda":
+        raise ValueError(f"component_stats: comp on {dev}, expected a GPU tensor")
+    n, C, K = comp.numel(), int(num_components), int(num_kinds)
+    if not 1 <= K <= COMPONENT_MAX_KINDS:
+        raise ValueError(f"component_stats: num_kinds {K} outside [1, {COMPONENT_MAX_KINDS}]")
+    if not 0 <= C < 1 << 31:
+        raise ValueError(f"component_stats: num_components {C} outside [0, 2^31)")
+    _require(comp, "comp", torch.int32, dev)
+    _require(kind, "kind", torch.uint8, dev, n)
+    if weight is not None:
+        _require(weight, "weight", torch.int32, dev, n)
+    if worst is not None:
+        _require(worst, "worst", torch.uint8, dev, n)
+    kind_counts = torch.zeros(C * K, dtype=torch.int32, device=dev)
+    weight_sum = torch.zeros(C, dtype=torch.int64, device=dev)
+    worst_min = torch.full((C,), -1, dtype=torch.int32, device=dev)
+    rc = lib.abom_component_stats(
+        _ptr(comp), _ptr(kind),
+        _ptr(weight) if weight is not None else None,
+        _ptr(worst) if worst is not None else None,
+        n, C, K, _ptr(kind_counts), _ptr(weight_sum), _ptr(worst_min), _stream(),
+    )
+    _check(rc, "abom_component_stats")
+    return kind_counts.view(C, K), weight_sum, worst_min
