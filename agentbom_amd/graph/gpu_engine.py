@@ -7,7 +7,13 @@ construction) and stays resident in HBM3E.  On top of it:
 - ``match()``            bulk advisory matching (ops/csrc/match.hip)
 - ``dependency_reach()`` multi-source BFS from all agents (ops/csrc/bfs.hip)
 - ``blast_counts()``     segmented joins: per-finding distinct agent/cred/
-                         tool reach with CWE-impact filtering
+                         tool reach with CWE-impact filtering.  On the GPU
+                         the matched packages are joined against a
+                         per-server reach index (``build_reach_index``: each
+                         server's distinct agents, creds and tools, laid out
+                         once with the CSR) by the two kernels of
+                         ops/csrc/blast.hip; AGENT_BOM_BLAST_INDEX=0 walks
+                         the CSR rows per package instead
 - ``score()``            GPU risk scoring (reference formula)
 - ``step()``             full findings pipeline: match -> reach -> join ->
                          score -> rank (the bench.py timed region)
@@ -180,6 +186,74 @@ def build_dedup_match_layout(torch, arena: dict, gk, hi, lo, flags):
     return layout
 
 
+def build_reach_index(torch, src, dst, et, server_base: int, n_servers: int,
+                      node_is_db_cred, node_is_db_tool) -> dict:
+    """Per-server reach index for the blast counts (ops/csrc/blast.hip).
+
+    A server's agents, creds and tools depend on the graph alone, so they
+    are filtered, deduplicated and laid out once, next to the CSR, instead of
+    once per visit of the server in every step.  Rows cover the server id
+    range, widened to every source of a CONTAINS edge, so a package's
+    containing server always has a row.  Layout:
+      row_base   node id of row 0
+      reach_col  int32 [T]: per row three consecutive segments -- distinct
+                 agents (reverse USES), distinct creds (forward HAS_CRED),
+                 distinct tools (forward PROVIDES_TOOL) -- each strictly
+                 ascending by node id
+      reach_off  int32 [S,4]: (agents begin, creds begin, tools begin, end);
+                 a row's end is the next row's agents begin
+      reach_db   int32 [S,2]: distinct creds with node_is_db_cred set,
+                 distinct tools with node_is_db_tool set
+    """
+    dev = src.device
+    lo, hi = int(server_base), int(server_base) + int(n_servers)
+    holders = src[et == ET_CONTAINS]
+    if holders.numel():
+        lo = min(lo, int(holders.min().item()))
+        hi = max(hi, int(holders.max().item()) + 1)
+    S = hi - lo
+
+    # one key per (row, segment, neighbour); unique() sorts and deduplicates
+    keys = []
+    for seg, (etype, row_node, nbr) in enumerate((
+            (ET_USES, dst, src), (ET_HAS_CRED, src, dst), (ET_PROVIDES_TOOL, src, dst))):
+        m = (et == etype) & (row_node >= lo) & (row_node < hi)
+        row = row_node[m].to(torch.int64) - lo
+        keys.append(((row * 3 + seg) << 32) | nbr[m].to(torch.int64))
+    key = torch.unique(torch.cat(keys))
+    slot = key >> 32  # row * 3 + segment
+    nbr = key & 0xFFFFFFFF
+    if key.numel() >= 2 ** 31:
+        raise ValueError("reach index exceeds int32 offsets")
+
+    bounds = torch.zeros(3 * S + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(slot, minlength=3 * S), 0, out=bounds[1:])
+    pick = 3 * torch.arange(S, device=dev).unsqueeze(1) + torch.arange(4, device=dev)
+    reach_off = bounds[pick].to(torch.int32).contiguous()
+
+    reach_db = torch.zeros(S, 2, dtype=torch.int64, device=dev)
+    row = slot // 3
+    seg = slot - 3 * row
+    for column, (which, flag) in enumerate(((1, node_is_db_cred), (2, node_is_db_tool))):
+        m = seg == which
+        reach_db[:, column].index_add_(0, row[m], flag[nbr[m]].to(torch.int64))
+    return {
+        "row_base": lo,
+        "reach_col": nbr.to(torch.int32).contiguous(),
+        "reach_off": reach_off,
+        "reach_db": reach_db.to(torch.int32).contiguous(),
+    }
+
+
+def blast_index_enabled() -> bool:
+    """A/B toggle: AGENT_BOM_BLAST_INDEX=0 makes ``_blast_counts_fused`` walk
+    the CSR rows per package (``native.blast_counts``) instead of joining
+    the packages against the per-server reach index."""
+    import os
+
+    return os.environ.get("AGENT_BOM_BLAST_INDEX", "1") != "0"
+
+
 def findings_native_enabled() -> bool:
     """A/B toggle: AGENT_BOM_FINDINGS_NATIVE=0 makes the GPU dedup path of
     ``EstateEngine.step`` assemble findings with the torch op chain
@@ -319,6 +393,13 @@ class EstateEngine:
             estate.tool_base + torch.arange(estate.n_tools, device=dev)
         ] = self.tool_is_db
 
+        # per-server reach index: a layout of the graph like fwd/rev, with
+        # their lifetime; the step joins every matched package against it
+        self._blast_ws: dict = {}
+        self.reach_index = build_reach_index(
+            torch, src, dst, et, estate.server_base, estate.n_servers,
+            self.node_is_db_cred, self.node_is_db_tool) if self.use_gpu else None
+
     def _build_csr(self, src, dst, et):
         """GPU CSR construction: stable sort by src, bincount offsets."""
         torch = self.torch
@@ -440,9 +521,11 @@ class EstateEngine:
     def blast_counts(self, finding_pkgs):
         """Per unique finding-package reach counts.
 
-        GPU path: ONE fused wave-per-package HIP kernel (ops/csrc/blast.hip);
-        zipf-head packages that overflow its LDS caps fall back to the exact
-        sort-based join below.  CPU path: the sort-based join throughout.
+        GPU path: the indexed kernels of ops/csrc/blast.hip (thread per
+        package from the per-server reach index, wave per multi-server
+        package); zipf-head packages that overflow the LDS caps fall back to
+        the exact sort-based join below.  CPU path: the sort-based join
+        throughout.
         Returns dense tensors indexed by position in ``uniq_pkgs``.
         """
         torch = self.torch
@@ -461,11 +544,19 @@ class EstateEngine:
         torch = self.torch
         if uniq_pkgs32 is None:
             uniq_pkgs32 = uniq_pkgs.to(torch.int32).contiguous()
-        counts, overflow = native.blast_counts(
-            uniq_pkgs32, self.rev, self.fwd,
-            (ET_CONTAINS, ET_USES, ET_HAS_CRED, ET_PROVIDES_TOOL),
-            self.node_is_db_cred, self.node_is_db_tool,
-        )
+        if self.reach_index is not None and blast_index_enabled():
+            # index path: the kernels count the overflowed rows, so nonzero()
+            # and the join below run only when there are any
+            counts, overflow, n_overflow = native.blast_counts_indexed(
+                uniq_pkgs32, self.rev, self.reach_index, ET_CONTAINS,
+                self.node_is_db_cred, self.node_is_db_tool, self._blast_ws)
+        else:
+            counts, overflow = native.blast_counts(
+                uniq_pkgs32, self.rev, self.fwd,
+                (ET_CONTAINS, ET_USES, ET_HAS_CRED, ET_PROVIDES_TOOL),
+                self.node_is_db_cred, self.node_is_db_tool,
+            )
+            n_overflow = None
         result = {
             "uniq_pkgs": uniq_pkgs,
             "n_servers": counts[:, 0].to(torch.int32),
@@ -475,6 +566,9 @@ class EstateEngine:
             "n_tools_all": counts[:, 4].to(torch.int32),
             "n_tools_db": counts[:, 5].to(torch.int32),
         }
+        if n_overflow == 0:
+            result["counts2d"] = counts
+            return result
         ov_idx = torch.nonzero(overflow).flatten()
         if ov_idx.numel():
             heavy = self._blast_counts_join(uniq_pkgs[ov_idx])

@@ -72,7 +72,8 @@ int abom_score_gather(
 int abom_severity_histogram(
     const void* owner, const void* severity, void* hist, long long n, void* stream);
 
-// blast.hip
+// blast.hip (the indexed entry point reads the per-server reach index and
+// leaves {queued packages, overflowed rows} in counters)
 int abom_blast_counts(
     const void* pkgs, long long n,
     const void* rev_off, const void* rev_col, const void* rev_et,
@@ -80,6 +81,13 @@ int abom_blast_counts(
     int et_contains, int et_uses, int et_cred, int et_tool,
     const void* node_is_db_cred, const void* node_is_db_tool,
     void* out_counts, void* out_overflow, void* stream);
+int abom_blast_counts_indexed(
+    const void* pkgs, long long n,
+    const void* rev_off, const void* rev_col, const void* rev_et, int et_contains,
+    const void* reach_off, const void* reach_col, const void* reach_db,
+    long long row_base, long long num_rows,
+    const void* node_is_db_cred, const void* node_is_db_tool,
+    void* queue, void* counters, void* out_counts, void* out_overflow, void* stream);
 
 // paths.hip (edge_weight and node_gate are nullable)
 int abom_path_relax(

@@ -1,7 +1,24 @@
 // Fused blast-radius reach counting on gfx950.
 //
-// Replaces the torch sort/unique/bincount join pipeline (gpu_engine.py
-// blast_counts — ~20 kernel launches per step) with ONE wave-cooperative
+// Two entry points, same outputs (six counts and an overflow flag per
+// package):
+//
+// abom_blast_counts_indexed — the engine's path.  A server's distinct
+// agents, creds and tools depend on the graph alone, so the engine lays them
+// out once per server (the reach index, built next to the CSR).  Pass A
+// (blast_index_fast_kernel, one thread per package, no LDS) finishes every
+// package with at most one distinct containing server straight from that
+// server's index row -- ~89 % of the matched packages of the benchmark
+// estate -- and queues the rest.  Pass B (blast_index_wave_kernel, one wave
+// per queued package) copies the index segments of the package's servers
+// into LDS and distinct-counts the unions.  The queue length stays on the
+// device; the kernels count the overflowed rows into one word, the only
+// thing the host reads.
+//
+// abom_blast_counts — for callers without an index (and the A/B knob
+// AGENT_BOM_BLAST_INDEX=0).  It replaced the torch sort/unique/bincount join
+// pipeline (gpu_engine.py _blast_counts_join — ~20 kernel launches per step)
+// with ONE wave-cooperative
 // kernel: each 64-lane wave owns one finding package and walks
 // package -> servers (reverse CONTAINS) -> {agents (reverse USES),
 // creds (forward EXPOSES_CRED), tools (forward PROVIDES_TOOL)} collecting
@@ -9,10 +26,13 @@
 // (O(m^2/64) first-occurrence scan — m is capped, LDS reads are 2 cycles).
 //
 // Zipf-head packages that overflow the LDS caps are flagged; the host
-// resolves just those with the sort-based path (hybrid, exact either way).
+// resolves just those with the sort-based path (hybrid, exact either way);
+// both entry points share the caps.
 // CDNA4 notes: one workgroup = 4 waves = 4 packages; LDS slice per wave =
-// (SRV_CAP + AG_CAP + CR_CAP + TL_CAP) * 4 B = 4.5 KiB -> 18 KiB/block,
-// sized so LDS is not the occupancy limiter (see cap comment below).
+// (SRV_CAP + AG_CAP + CR_CAP + TL_CAP) * 4 B = 4.25 KiB -> 17 KiB/block,
+// sized so LDS is not the occupancy limiter (see cap comment below); the
+// indexed wave kernel adds a 64-entry server chunk and the per-server
+// segment tables, 6 KiB per wave -> 24 KiB/block.
 
 #include "abom_api.h"
 #include "abom_common.h"
@@ -182,7 +202,268 @@ __global__ void __launch_bounds__(256) blast_count_kernel(
     }
 }
 
+// ── indexed path ───────────────────────────────────────────────────────────
+//
+// reach_off / reach_col / reach_db are the per-server reach index that
+// EstateEngine builds once next to the CSR (graph/gpu_engine.py
+// build_reach_index): row r = server node id - row_base, reach_off[r] =
+// (agents begin, creds begin, tools begin, end) into reach_col, every segment
+// ascending and duplicate-free, reach_db[r] = (db creds, db tools).
+
+constexpr uint32_t NO_SERVER = 0xFFFFFFFFu;
+
+__device__ __forceinline__ void write_counts(
+    uint32_t* __restrict__ out_counts, long long p, uint32_t srv, uint32_t ag,
+    uint32_t cr, uint32_t cr_db, uint32_t tl, uint32_t tl_db) {
+    uint2* row = reinterpret_cast<uint2*>(out_counts + p * 6);  // 24 B rows
+    row[0] = make_uint2(srv, ag);
+    row[1] = make_uint2(cr, cr_db);
+    row[2] = make_uint2(tl, tl_db);
+}
+
+// Pass A: one thread per package.  Packages with no or one distinct
+// containing server are finished here from the index row alone (no LDS, no
+// set operation); the rest are queued for the wave kernel.  counters[0] is
+// the queue length, counters[1] the number of overflowed rows.
+__global__ void __launch_bounds__(256) blast_index_fast_kernel(
+    const uint32_t* __restrict__ pkgs, long long n,
+    const uint64_t* __restrict__ rev_off, const uint32_t* __restrict__ rev_col,
+    const uint8_t* __restrict__ rev_et, uint8_t et_contains,
+    const int4* __restrict__ reach_off, const int2* __restrict__ reach_db,
+    uint32_t row_base, uint32_t num_rows,
+    uint32_t* __restrict__ queue, unsigned int* __restrict__ counters,
+    uint32_t* __restrict__ out_counts, uint8_t* __restrict__ out_overflow) {
+    const int lane = threadIdx.x & 63;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long start = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    // wave-uniform trip count: every lane reaches the ballots below
+    for (long long base = start - lane; base < n; base += stride) {
+        const long long p = base + lane;
+        const bool active = p < n;
+        uint32_t first = NO_SERVER;
+        bool multi = false;
+        if (active) {
+            const uint32_t pkg = pkgs[p];
+            const uint64_t beg = rev_off[pkg];
+            const uint64_t end = rev_off[pkg + 1];
+            for (uint64_t e = beg; e < end; ++e) {
+                if (rev_et[e] != et_contains) continue;
+                const uint32_t s = rev_col[e];
+                if (first == NO_SERVER) {
+                    first = s;
+                } else if (s != first) {
+                    multi = true;
+                    break;
+                }
+            }
+        }
+        // a server outside the index cannot be answered here: flag the row,
+        // the caller's exact join takes it
+        const bool outside = active && !multi && first != NO_SERVER &&
+                             first - row_base >= num_rows;
+        if (active && !multi && !outside) {
+            if (first == NO_SERVER) {
+                write_counts(out_counts, p, 0, 0, 0, 0, 0, 0);
+            } else {
+                const int4 off = reach_off[first - row_base];
+                const int2 db = reach_db[first - row_base];
+                write_counts(out_counts, p, 1, (uint32_t)(off.y - off.x),
+                             (uint32_t)(off.z - off.y), (uint32_t)db.x,
+                             (uint32_t)(off.w - off.z), (uint32_t)db.y);
+            }
+            out_overflow[p] = 0;
+        }
+        if (outside) {
+            write_counts(out_counts, p, 0, 0, 0, 0, 0, 0);
+            out_overflow[p] = 1;
+        }
+        // one atomic per wave and counter
+        const unsigned long long qmask = __ballot(multi);
+        if (qmask) {
+            const int leader = __ffsll((long long)qmask) - 1;
+            unsigned int qbase = 0;
+            if (lane == leader) qbase = atomicAdd(&counters[0], (unsigned int)__popcll(qmask));
+            qbase = __shfl(qbase, leader, 64);
+            if (multi) queue[qbase + __popcll(qmask & ((1ull << lane) - 1))] = (uint32_t)p;
+        }
+        const unsigned long long omask = __ballot(outside);
+        if (omask && lane == __ffsll((long long)omask) - 1)
+            atomicAdd(&counters[1], (unsigned int)__popcll(omask));
+    }
+}
+
+__device__ __forceinline__ int wave_exclusive_scan(int v, int lane, int* total) {
+    int incl = v;
+    for (int off = 1; off < 64; off <<= 1) {
+        const int up = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += up;
+    }
+    *total = __shfl(incl, 63, 64);
+    return incl - v;
+}
+
+// Copy the index segments of the wave's servers into dst[0..total): entry i
+// belongs to the last server s with pref[s] <= i (pref = exclusive prefix of
+// the segment lengths), at reach_col[beg[s] + i - pref[s]].
+__device__ __forceinline__ void gather_segments(
+    const int* beg, const int* pref, int n_srv, int total,
+    const uint32_t* __restrict__ reach_col, uint32_t* dst, int lane) {
+    for (int i = lane; i < total; i += 64) {
+        int lo = 0, hi = n_srv;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (pref[mid] <= i) lo = mid; else hi = mid;
+        }
+        dst[i] = reach_col[beg[lo] + (i - pref[lo])];
+    }
+}
+
+// Pass B: one wave per queued package (two or more containing servers).
+// The grid reads the queue length from device memory, so no host read sits
+// between the passes.
+__global__ void __launch_bounds__(256) blast_index_wave_kernel(
+    const uint32_t* __restrict__ pkgs,
+    const uint64_t* __restrict__ rev_off, const uint32_t* __restrict__ rev_col,
+    const uint8_t* __restrict__ rev_et, uint8_t et_contains,
+    const int4* __restrict__ reach_off, const uint32_t* __restrict__ reach_col,
+    uint32_t row_base, uint32_t num_rows,
+    const uint8_t* __restrict__ node_is_db_cred,
+    const uint8_t* __restrict__ node_is_db_tool,
+    const uint32_t* __restrict__ queue, unsigned int* __restrict__ counters,
+    uint32_t* __restrict__ out_counts, uint8_t* __restrict__ out_overflow) {
+    // servers: SRV_CAP distinct ones plus one 64-edge chunk being deduplicated
+    __shared__ uint32_t lds_srv[WAVES_PER_BLOCK][SRV_CAP + 64];
+    __shared__ int lds_beg[WAVES_PER_BLOCK][3][SRV_CAP];
+    __shared__ int lds_pref[WAVES_PER_BLOCK][3][SRV_CAP];
+    __shared__ uint32_t lds_ag[WAVES_PER_BLOCK][AG_CAP];
+    __shared__ uint32_t lds_cr[WAVES_PER_BLOCK][CR_CAP];
+    __shared__ uint32_t lds_tl[WAVES_PER_BLOCK][TL_CAP];
+
+    const int lane = threadIdx.x & 63;
+    const int wid = threadIdx.x >> 6;
+    const long long wave_global = (long long)blockIdx.x * WAVES_PER_BLOCK + wid;
+    const long long n_waves = (long long)gridDim.x * WAVES_PER_BLOCK;
+    const long long n_queued = counters[0];
+    uint32_t* srv = lds_srv[wid];
+
+    for (long long q = wave_global; q < n_queued; q += n_waves) {
+        const long long p = queue[q];
+        const uint32_t pkg = pkgs[p];
+        bool overflow = false;
+
+        // distinct containing servers, in first-seen order
+        int n_srv = 0;
+        const uint64_t beg = rev_off[pkg];
+        const uint64_t end = rev_off[pkg + 1];
+        for (uint64_t base = beg; base < end && !overflow; base += 64) {
+            const uint64_t e = base + lane;
+            const bool valid = e < end && rev_et[e] == et_contains;
+            const uint32_t v = valid ? rev_col[e] : 0u;
+            const unsigned long long mask = __ballot(valid);
+            const int rank = __popcll(mask & ((1ull << lane) - 1));
+            if (valid) srv[n_srv + rank] = v;  // n_srv <= SRV_CAP: inside the chunk area
+            __builtin_amdgcn_wave_barrier();
+            bool first = valid;
+            if (valid) {
+                for (int j = 0; j < n_srv + rank; ++j) {
+                    if (srv[j] == v) { first = false; break; }
+                }
+            }
+            // out-of-index servers cannot be joined here
+            if (first && v - row_base >= num_rows) overflow = true;
+            const unsigned long long fmask = __ballot(first);
+            __builtin_amdgcn_wave_barrier();  // all reads above precede the compaction
+            if (first) srv[n_srv + __popcll(fmask & ((1ull << lane) - 1))] = v;
+            __builtin_amdgcn_wave_barrier();
+            n_srv += __popcll(fmask);
+            if (n_srv > SRV_CAP) overflow = true;
+            overflow = __ballot(overflow) != 0;
+        }
+
+        int n_ag = 0, n_cr = 0, n_tl = 0;
+        if (!overflow) {
+            // one lane per server: its index row, then the three prefix sums
+            int4 off = make_int4(0, 0, 0, 0);
+            if (lane < n_srv) off = reach_off[srv[lane] - row_base];
+            const int p_ag = wave_exclusive_scan(off.y - off.x, lane, &n_ag);
+            const int p_cr = wave_exclusive_scan(off.z - off.y, lane, &n_cr);
+            const int p_tl = wave_exclusive_scan(off.w - off.z, lane, &n_tl);
+            overflow = n_ag > AG_CAP || n_cr > CR_CAP || n_tl > TL_CAP;
+            if (!overflow) {
+                lds_beg[wid][0][lane] = off.x; lds_pref[wid][0][lane] = p_ag;
+                lds_beg[wid][1][lane] = off.y; lds_pref[wid][1][lane] = p_cr;
+                lds_beg[wid][2][lane] = off.z; lds_pref[wid][2][lane] = p_tl;
+                __builtin_amdgcn_wave_barrier();
+                gather_segments(lds_beg[wid][0], lds_pref[wid][0], n_srv, n_ag,
+                                reach_col, lds_ag[wid], lane);
+                gather_segments(lds_beg[wid][1], lds_pref[wid][1], n_srv, n_cr,
+                                reach_col, lds_cr[wid], lane);
+                gather_segments(lds_beg[wid][2], lds_pref[wid][2], n_srv, n_tl,
+                                reach_col, lds_tl[wid], lane);
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+
+        if (overflow) {
+            if (lane == 0) {
+                out_overflow[p] = 1;
+                write_counts(out_counts, p, 0, 0, 0, 0, 0, 0);
+                atomicAdd(&counters[1], 1u);
+            }
+            continue;
+        }
+
+        int ag_all, ag_db, cr_all, cr_db, tl_all, tl_db;
+        distinct_count(lds_ag[wid], n_ag, nullptr, lane, &ag_all, &ag_db);
+        distinct_count(lds_cr[wid], n_cr, node_is_db_cred, lane, &cr_all, &cr_db);
+        distinct_count(lds_tl[wid], n_tl, node_is_db_tool, lane, &tl_all, &tl_db);
+
+        if (lane == 0) {
+            out_overflow[p] = 0;
+            write_counts(out_counts, p, (uint32_t)n_srv, (uint32_t)ag_all,
+                         (uint32_t)cr_all, (uint32_t)cr_db, (uint32_t)tl_all,
+                         (uint32_t)tl_db);
+        }
+    }
+}
+
 }  // namespace abom
+
+extern "C" int abom_blast_counts_indexed(
+    const void* pkgs, long long n,
+    const void* rev_off, const void* rev_col, const void* rev_et, int et_contains,
+    const void* reach_off, const void* reach_col, const void* reach_db,
+    long long row_base, long long num_rows,
+    const void* node_is_db_cred, const void* node_is_db_tool,
+    void* queue, void* counters, void* out_counts, void* out_overflow, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    ABOM_CHECK(hipMemsetAsync(counters, 0, 2 * sizeof(unsigned int), s));
+    if (n <= 0) return 0;
+    const int block = 256;
+    hipLaunchKernelGGL(abom::blast_index_fast_kernel, dim3(abom::grid_for(n, block)),
+                       dim3(block), 0, s,
+                       (const uint32_t*)pkgs, n,
+                       (const uint64_t*)rev_off, (const uint32_t*)rev_col,
+                       (const uint8_t*)rev_et, (uint8_t)et_contains,
+                       (const int4*)reach_off, (const int2*)reach_db,
+                       (uint32_t)row_base, (uint32_t)num_rows,
+                       (uint32_t*)queue, (unsigned int*)counters,
+                       (uint32_t*)out_counts, (uint8_t*)out_overflow);
+    ABOM_CHECK(hipGetLastError());
+    // the queue length is known on the device only: size the grid for the
+    // worst case (every package queued) and let the waves stride over it
+    hipLaunchKernelGGL(abom::blast_index_wave_kernel,
+                       dim3(abom::grid_for(n, abom::WAVES_PER_BLOCK)), dim3(block), 0, s,
+                       (const uint32_t*)pkgs,
+                       (const uint64_t*)rev_off, (const uint32_t*)rev_col,
+                       (const uint8_t*)rev_et, (uint8_t)et_contains,
+                       (const int4*)reach_off, (const uint32_t*)reach_col,
+                       (uint32_t)row_base, (uint32_t)num_rows,
+                       (const uint8_t*)node_is_db_cred, (const uint8_t*)node_is_db_tool,
+                       (const uint32_t*)queue, (unsigned int*)counters,
+                       (uint32_t*)out_counts, (uint8_t*)out_overflow);
+    return (int)hipGetLastError();
+}
 
 extern "C" int abom_blast_counts(
     const void* pkgs, long long n,

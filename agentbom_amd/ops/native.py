@@ -93,6 +93,14 @@ _SIGNATURES = {
         _c, _c,                  # node_is_db_cred, node_is_db_tool
         _c, _c, _c,              # out_counts, out_overflow, stream
     ], _i32),
+    "abom_blast_counts_indexed": ([
+        _c, _i64,            # pkgs, n
+        _c, _c, _c, _i32,    # rev_off, rev_col, rev_et, et_contains
+        _c, _c, _c,          # reach_off, reach_col, reach_db
+        _i64, _i64,          # row_base, num_rows
+        _c, _c,              # node_is_db_cred, node_is_db_tool
+        _c, _c, _c, _c, _c,  # queue, counters, out_counts, out_overflow, stream
+    ], _i32),
     "abom_path_relax": ([
         _c, _c, _c, _c,  # edge_src, col, etype, edge_weight
         _c, _c, _c, _c,  # cur, nxt, node_boost, etype_boost
@@ -572,6 +580,38 @@ def blast_counts(pkgs, rev, fwd, et_codes: tuple[int, int, int, int],
     )
     _check(rc, "abom_blast_counts")
     return out_counts.view(n, 6), out_overflow
+
+
+def blast_counts_indexed(pkgs, rev, index: dict, et_contains: int,
+                         node_is_db_cred, node_is_db_tool, workspace: dict):
+    """Per-package reach counts from the per-server reach index
+    (``graph.gpu_engine.build_reach_index``): a thread-per-package pass that
+    finishes packages with at most one containing server and queues the rest
+    for a wave-per-package pass.  Returns (counts [n,6] int32, overflow u8
+    [n], number of overflowed rows); the one host read is that number.  The
+    two kernels write every row, so the outputs are not pre-filled.
+    ``workspace["counters"]`` keeps {queued packages, overflowed rows} of the
+    last call."""
+    import torch
+
+    lib = load()
+    n = pkgs.numel()
+    dev = pkgs.device
+    out_counts = torch.empty(n * 6, dtype=torch.int32, device=dev)
+    out_overflow = torch.empty(n, dtype=torch.uint8, device=dev)
+    queue = _buf(workspace, "queue", n, torch.int32, dev)
+    counters = _buf(workspace, "counters", 2, torch.int32, dev)
+    rc = lib.abom_blast_counts_indexed(
+        _ptr(pkgs), n,
+        _ptr(rev["row_off"]), _ptr(rev["col"]), _ptr(rev["etype"]), et_contains,
+        _ptr(index["reach_off"]), _ptr(index["reach_col"]), _ptr(index["reach_db"]),
+        index["row_base"], index["reach_off"].shape[0],
+        _ptr(node_is_db_cred), _ptr(node_is_db_tool),
+        _ptr(queue), _ptr(counters), _ptr(out_counts), _ptr(out_overflow), _stream(),
+    )
+    _check(rc, "abom_blast_counts_indexed")
+    n_overflow = int(counters[1].item())
+    return out_counts.view(n, 6), out_overflow, n_overflow
 
 
 def risk_weights_array() -> np.ndarray:
