@@ -4,7 +4,16 @@ The estate graph (agents, servers, creds, tools, packages) is built as
 forward and reverse CSR on-device (torch sort/bincount/cumsum — GPU CSR
 construction) and stays resident in HBM3E.  On top of it:
 
-- ``match()``            bulk advisory matching (ops/csrc/match.hip)
+- ``match()``            bulk advisory matching (ops/csrc/match.hip), one
+                         thread per package row walking the windows of its
+                         group (``match_kernel``).  ``step()`` matches the
+                         DISTINCT rows of the dedup layout instead, with one
+                         thread per advisory window binary-searching the
+                         group's rows in a search table built once
+                         (``build_match_search_table``,
+                         ``match_by_window_kernel``);
+                         AGENT_BOM_MATCH_BY_WINDOW=0, or an estate without a
+                         dedup layout, keeps the row kernel there
 - ``dependency_reach()`` multi-source BFS from all agents (ops/csrc/bfs.hip)
 - ``blast_counts()``     segmented joins: per-finding distinct agent/cred/
                          tool reach with CWE-impact filtering.  On the GPU
@@ -142,7 +151,9 @@ def build_dedup_match_layout(torch, arena: dict, gk, hi, lo, flags):
         "row_of": row_of_from_runs(torch, run_off, idx),
     }
     layout["u_ranges"] = _precompute_win_ranges(torch, arena, layout["u_gk"])
-    # Match schedule experiments (AGENT_BOM_MATCH_SCHEDULE):
+    # Match schedule experiments (AGENT_BOM_MATCH_SCHEDULE).  They order the
+    # rows of the row kernel (match_kernel) only: the window-per-thread
+    # kernel visits windows, not rows, and ignores ``heavy_order``.
     #   row   — rows in window-count-descending order.  Measured SLOWER
     #           (2.44 vs 2.27 ms/step): equal-wcnt rows from DIFFERENT
     #           groups interleave, so wave lanes stop sharing a window
@@ -184,6 +195,55 @@ def build_dedup_match_layout(torch, arena: dict, gk, hi, lo, flags):
     else:
         layout["heavy_order"] = None
     return layout
+
+
+def build_match_search_table(torch, arena: dict, layout: dict) -> dict:
+    """Row search table of the window-per-thread match (ops/csrc/match.hip,
+    ``match_by_window_kernel``): the layout's distinct rows regrouped by
+    advisory group and sorted by version key, so that the rows a window
+    matches are one contiguous run and two or three binary searches find it.
+
+    Like ``pkg_win_range`` this joins estate rows to arena groups by name and
+    nothing else: no version key is compared with a window bound here, every
+    such test runs in the kernel in every step.  Holds the rows with
+    PF_ENCODABLE set and a non-empty window range, ordered by (arena group,
+    key hi, key lo, row id) with the key as unsigned 128 bits -- the layout's
+    own order compares signed int64, which misplaces a key with bit 63 set in
+    either word, so the order is rebuilt here with the sign bit flipped.
+      s_key    int64 [R,2]: (hi, lo) bit patterns, one 16-byte probe per row
+      s_row    int32 [R]: the row's index in the layout's ``u_*`` columns
+      w_rbeg   int32 [W]: for every arena window the run of its group in
+      w_rend   int32 [W]  ``s_*``; empty when no estate row has the name
+    """
+    from agentbom_amd.ops.cpu_ref import PF_ENCODABLE
+
+    gk = arena["group_keys"]
+    group_off = arena["group_off"].to(torch.int64) & 0xFFFFFFFF
+    G = gk.numel()
+    dev = gk.device
+    W = arena["windows"]["flags"].numel()
+    wbeg, wend = layout["u_ranges"]
+    keep = ((layout["u_flags"] & PF_ENCODABLE) != 0) & (wend != wbeg)
+    rows = torch.nonzero(keep).flatten()  # ascending row id
+    if rows.numel() >= 2 ** 31 or W >= 2 ** 31:
+        raise ValueError("match search table exceeds int32 offsets")
+    # a kept row has windows, so its name is one of the arena's group keys
+    grp = torch.searchsorted(gk ^ _SIGN64, layout["u_gk"][rows] ^ _SIGN64)
+    hi, lo = layout["u_hi"][rows], layout["u_lo"][rows]
+    # stable sorts from the least significant column up; ties keep row order
+    order = torch.argsort(lo ^ _SIGN64, stable=True)
+    order = order[torch.argsort((hi ^ _SIGN64)[order], stable=True)]
+    order = order[torch.argsort(grp[order], stable=True)]
+    run_off = torch.zeros(G + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(grp, minlength=G), 0, out=run_off[1:])
+    win_grp = torch.repeat_interleave(
+        torch.arange(G, device=dev), group_off[1:] - group_off[:-1])
+    return {
+        "s_key": torch.stack([hi[order], lo[order]], dim=1).contiguous(),
+        "s_row": rows[order].to(torch.int32).contiguous(),
+        "w_rbeg": run_off[win_grp].to(torch.int32).contiguous(),
+        "w_rend": run_off[win_grp + 1].to(torch.int32).contiguous(),
+    }
 
 
 def build_reach_index(torch, src, dst, et, server_base: int, n_servers: int,
@@ -252,6 +312,16 @@ def blast_index_enabled() -> bool:
     import os
 
     return os.environ.get("AGENT_BOM_BLAST_INDEX", "1") != "0"
+
+
+def match_by_window_enabled() -> bool:
+    """A/B toggle: AGENT_BOM_MATCH_BY_WINDOW=0 makes the dedup path of
+    ``EstateEngine.step`` match with one thread per distinct row
+    (``native.match_launch``) instead of one thread per advisory window over
+    the row search table (``native.match_by_window_launch``)."""
+    import os
+
+    return os.environ.get("AGENT_BOM_MATCH_BY_WINDOW", "1") != "0"
 
 
 def findings_native_enabled() -> bool:
@@ -373,6 +443,11 @@ class EstateEngine:
         self.match_dedup = build_dedup_match_layout(
             torch, self.arena, self.pkg_group_key, self.pkg_key_hi,
             self.pkg_key_lo, self.pkg_flags) if self.use_gpu else None
+        # row search table of the window-per-thread match: the distinct rows
+        # of every advisory group in version-key order, built once like the
+        # layout it indexes
+        self.match_table = build_match_search_table(
+            torch, self.arena, self.match_dedup) if self.match_dedup is not None else None
         self.cred_is_db = torch.from_numpy(estate.cred_is_db).to(dev)
         self.tool_is_db = torch.from_numpy(estate.tool_is_db).to(dev)
         self.cred_lut = torch.from_numpy(_impact_lut(_FULL_CRED, _DB_CRED)).to(dev)
@@ -635,7 +710,14 @@ class EstateEngine:
             side.wait_stream(torch.cuda.current_stream())
             dd = self.match_dedup
             with torch.cuda.stream(side):
-                if dd is not None:
+                if (dd is not None and self.match_table is not None
+                        and match_by_window_enabled()):
+                    # dedup-match by window: every advisory window searches
+                    # the sorted distinct rows of its group; pairs are keyed
+                    # by distinct row, as below
+                    pending = native.match_by_window_launch(
+                        self.arena["windows"], self.match_table)
+                elif dd is not None:
                     # dedup-match: one kernel row per DISTINCT (name,
                     # version); results fan back out below
                     pending = native.match_launch(

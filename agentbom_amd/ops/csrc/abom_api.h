@@ -28,6 +28,14 @@ int abom_match(
     const void* w_last_hi, const void* w_last_lo, const void* w_flags, const void* w_packed,
     const void* pkg_wbeg, const void* pkg_wend, const void* p_order,
     void* out_pairs, void* out_count, long long capacity, void* stream);
+// one thread per window over the row search table (s_key int64 [R,2], s_row
+// int32 [R]; [w_rbeg, w_rend) is a window's run of rows); same pair output
+int abom_match_by_window(
+    const void* w_intro_hi, const void* w_intro_lo, const void* w_fixed_hi, const void* w_fixed_lo,
+    const void* w_last_hi, const void* w_last_lo, const void* w_flags,
+    const void* w_rbeg, const void* w_rend, long long num_windows,
+    const void* s_key, const void* s_row,
+    void* out_pairs, void* out_count, long long capacity, void* stream);
 
 // bfs.hip (abom_bfs_run returns the number of levels run or a negated hipError_t)
 int abom_bfs_expand(

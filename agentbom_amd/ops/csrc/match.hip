@@ -19,11 +19,29 @@
 // - packages with unencodable versions are skipped (PF_ENCODABLE off) and
 //   resolved on the host the same way.
 //
-// Each thread owns one package: binary-search the sorted group_key array
-// (top of the tree stays L2/L3-resident), then walk that group's windows
-// testing the package's u128 key against each window's bounds.  Matches are
-// appended through a device atomic cursor as (pkg_idx << 32 | window_idx);
-// the caller sorts the pairs for deterministic downstream ordering.
+// Two kernels answer the same question, which (row, window) pairs match:
+//
+// match_kernel: each thread owns one package row: binary-search the sorted
+// group_key array (top of the tree stays L2/L3-resident; skipped when the
+// caller hands in precomputed window ranges), then walk that group's
+// windows testing the row's u128 key against each window's bounds.  It needs
+// nothing but the rows and the arena, so it serves native.match, the
+// non-dedup and distributed engines and every caller without a search table;
+// on the dedup path of EstateEngine.step it runs when
+// AGENT_BOM_MATCH_BY_WINDOW=0.
+//
+// match_by_window_kernel: each thread owns one WINDOW.  The distinct rows of
+// a group, sorted by unsigned (hi, lo) key in a search table built once with
+// the engine (graph/gpu_engine.py::build_match_search_table), make a
+// window's match set a contiguous run of rows: two or three binary searches
+// find its ends, where the row kernel tests every (row, window) pair of the
+// group.  The default of EstateEngine.step whenever the estate has a dedup
+// layout.  Every key-against-bound comparison still happens in the kernel,
+// every step; the table only joins rows to groups by name.
+//
+// Both append matches through a device atomic cursor as
+// (row_idx << 32 | window_idx), in no particular order; the caller sorts the
+// pairs, or hands them to the finding assembly, which needs no order.
 
 #include "abom_api.h"
 #include "abom_common.h"
@@ -179,6 +197,71 @@ __global__ void match_kernel(
     }
 }
 
+// First row in [lo, hi) whose key is >= (bhi, blo), or > it when `after`.
+// Probes are one 16-byte load each; the rows of the run ascend by key.
+__device__ __forceinline__ uint32_t row_bound(const ulonglong2* __restrict__ s_key,
+                                              uint32_t lo, uint32_t hi,
+                                              uint64_t bhi, uint64_t blo, bool after) {
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        const ulonglong2 k = s_key[mid];  // x = hi word, y = lo word
+        const bool before = after ? !key_lt(bhi, blo, k.x, k.y) : key_lt(k.x, k.y, bhi, blo);
+        if (before) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// One thread per advisory window.  [w_rbeg[w], w_rend[w]) is the run of the
+// window's group in the search table (s_key ascending within the run,
+// s_row the row's index in the dedup layout); an empty run means that no
+// encodable estate row carries the group's name.
+__global__ void match_by_window_kernel(
+    const uint64_t* __restrict__ w_intro_hi,      // [W]
+    const uint64_t* __restrict__ w_intro_lo,
+    const uint64_t* __restrict__ w_fixed_hi,
+    const uint64_t* __restrict__ w_fixed_lo,
+    const uint64_t* __restrict__ w_last_hi,
+    const uint64_t* __restrict__ w_last_lo,
+    const uint8_t* __restrict__ w_flags,
+    const uint32_t* __restrict__ w_rbeg,          // [W]
+    const uint32_t* __restrict__ w_rend,          // [W]
+    long long num_windows,
+    const ulonglong2* __restrict__ s_key,         // [R] (hi, lo)
+    const int* __restrict__ s_row,                // [R]
+    uint64_t* __restrict__ out_pairs,             // [capacity]
+    unsigned int* __restrict__ out_count,
+    long long capacity) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x; w < num_windows;
+         w += stride) {
+        const uint8_t f = w_flags[w];
+        if (f & (WF_CPU_FALLBACK | WF_UNFIXED_SUPPRESSED)) continue;
+        const uint32_t rbeg = w_rbeg[w], rend = w_rend[w];
+        if (rbeg >= rend) continue;
+        // intro inclusive, fixed exclusive, last inclusive.  The end searches
+        // start at `begin`: a bound below it gives end == begin, the same
+        // empty result as its true position further left.
+        uint32_t begin = rbeg, end = rend;
+        if (f & WF_HAS_INTRO)
+            begin = row_bound(s_key, rbeg, rend, w_intro_hi[w], w_intro_lo[w], false);
+        if (f & WF_HAS_FIXED)
+            end = row_bound(s_key, begin, end, w_fixed_hi[w], w_fixed_lo[w], false);
+        if (f & WF_HAS_LAST)
+            end = row_bound(s_key, begin, end, w_last_hi[w], w_last_lo[w], true);
+        if (begin >= end) continue;
+        // one reservation for the whole run; the count keeps growing past
+        // capacity (the caller relaunches), the stores do not
+        const uint32_t n = end - begin;
+        const unsigned base = atomicAdd(out_count, n);
+        for (uint32_t j = 0; j < n; ++j) {
+            if ((long long)base + j < capacity) {
+                out_pairs[(long long)base + j] =
+                    ((uint64_t)(uint32_t)s_row[begin + j] << 32) | (uint64_t)w;
+            }
+        }
+    }
+}
+
 }  // namespace abom
 
 namespace abom {
@@ -221,5 +304,27 @@ extern "C" int abom_match(
                        (const int*)p_order,
                        (uint64_t*)out_pairs,
                        (unsigned int*)out_count, capacity);
+    return (int)hipGetLastError();
+}
+
+extern "C" int abom_match_by_window(
+    const void* w_intro_hi, const void* w_intro_lo,
+    const void* w_fixed_hi, const void* w_fixed_lo,
+    const void* w_last_hi, const void* w_last_lo,
+    const void* w_flags,
+    const void* w_rbeg, const void* w_rend, long long num_windows,
+    const void* s_key, const void* s_row,
+    void* out_pairs, void* out_count, long long capacity, void* stream) {
+    const int block = 256;
+    const int grid = abom::grid_for(num_windows, block);
+    hipLaunchKernelGGL(abom::match_by_window_kernel, dim3(grid), dim3(block), 0,
+                       (hipStream_t)stream,
+                       (const uint64_t*)w_intro_hi, (const uint64_t*)w_intro_lo,
+                       (const uint64_t*)w_fixed_hi, (const uint64_t*)w_fixed_lo,
+                       (const uint64_t*)w_last_hi, (const uint64_t*)w_last_lo,
+                       (const uint8_t*)w_flags,
+                       (const uint32_t*)w_rbeg, (const uint32_t*)w_rend, num_windows,
+                       (const ulonglong2*)s_key, (const int*)s_row,
+                       (uint64_t*)out_pairs, (unsigned int*)out_count, capacity);
     return (int)hipGetLastError();
 }

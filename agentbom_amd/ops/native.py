@@ -42,6 +42,13 @@ _SIGNATURES = {
         _c, _c, _c,        # pkg_wbeg, pkg_wend, p_order
         _c, _c, _i64, _c,  # out_pairs, out_count, capacity, stream
     ], _i32),
+    "abom_match_by_window": ([
+        _c, _c, _c, _c,    # w_intro_hi, w_intro_lo, w_fixed_hi, w_fixed_lo
+        _c, _c, _c,        # w_last_hi, w_last_lo, w_flags
+        _c, _c, _i64,      # w_rbeg, w_rend, num_windows
+        _c, _c,            # s_key, s_row
+        _c, _c, _i64, _c,  # out_pairs, out_count, capacity, stream
+    ], _i32),
     "abom_bfs_expand": ([
         _c, _c, _c, _u32,    # row_off, col, etype, allowed_mask
         _c, _i64, _c, _u32,  # frontier, frontier_size, dist, next_level
@@ -286,16 +293,57 @@ def match_launch(pkg_group_key, pkg_key_hi, pkg_key_lo, pkg_flags, group_keys,
     )
     _check(rc, "abom_match")
     return {"out_pairs": out_pairs, "out_count": out_count, "cap": cap,
-            "args": (pkg_group_key, pkg_key_hi, pkg_key_lo, pkg_flags,
-                     group_keys, group_off, windows),
-            "kw": {"pkg_win_range": pkg_win_range, "order": order}}
+            "relaunch": lambda capacity: match_launch(
+                pkg_group_key, pkg_key_hi, pkg_key_lo, pkg_flags, group_keys,
+                group_off, windows, capacity=capacity,
+                pkg_win_range=pkg_win_range, order=order)}
+
+
+def match_by_window_launch(windows: dict, table: dict,
+                           capacity: Optional[int] = None) -> dict:
+    """Launch the window-per-thread match on the CURRENT stream without
+    syncing: every arena window binary-searches the run of its group in the
+    row search table (``graph.gpu_engine.build_match_search_table``).
+
+    Returns the same pending handle as :func:`match_launch`, for
+    :func:`match_finalize` and :func:`assemble_findings`; the pairs carry the
+    table's ``s_row`` (the row's index in the dedup layout), in no particular
+    order.  On overflow the handle relaunches this kernel.
+    """
+    import torch
+
+    lib = load()
+    flags = windows["flags"]
+    W = flags.numel()
+    R = table["s_row"].numel()
+    if W >= 1 << 32:
+        raise ValueError(f"match: {W} windows exceeds the u32 pair encoding")
+    if table["w_rbeg"].numel() != W or table["w_rend"].numel() != W:
+        raise ValueError("match: search table was built for another arena")
+    cap = capacity or max(1024, R // 4)
+    dev = flags.device
+    out_pairs = torch.empty(cap, dtype=torch.int64, device=dev)
+    out_count = torch.zeros(1, dtype=torch.int32, device=dev)
+    rc = lib.abom_match_by_window(
+        _ptr(windows["intro_hi"]), _ptr(windows["intro_lo"]),
+        _ptr(windows["fixed_hi"]), _ptr(windows["fixed_lo"]),
+        _ptr(windows["last_hi"]), _ptr(windows["last_lo"]), _ptr(flags),
+        _ptr(table["w_rbeg"]), _ptr(table["w_rend"]), W,
+        _ptr(table["s_key"]), _ptr(table["s_row"]),
+        _ptr(out_pairs), _ptr(out_count), cap, _stream(),
+    )
+    _check(rc, "abom_match_by_window")
+    return {"out_pairs": out_pairs, "out_count": out_count, "cap": cap,
+            "relaunch": lambda capacity: match_by_window_launch(
+                windows, table, capacity=capacity)}
 
 
 def match_finalize(pending: dict, sort: bool = True):
     """Read the pending match count and produce (pkg_idx, win_idx).
 
-    On capacity overflow (count > cap) the match is relaunched synchronously
-    with a grown buffer — rare, the launch heuristic is P//4.
+    On capacity overflow (count > cap) the handle's ``relaunch`` runs the
+    kernel that filled it again, synchronously, with a grown buffer — rare,
+    the launch heuristic is P//4.
 
     ``sort=False`` skips the canonical (pkg<<32|win) sort — for callers that
     impose their own order downstream (the dedup-expand path re-sorts after
@@ -310,8 +358,7 @@ def match_finalize(pending: dict, sort: bool = True):
         # rather than slicing with a wrapped count.
         raise RuntimeError("match: device match count overflowed int32; shard the package batch")
     if n > pending["cap"]:
-        relaunched = match_launch(*pending["args"], capacity=int(n * 1.2) + 1024,
-                                  **pending.get("kw", {}))
+        relaunched = pending["relaunch"](int(n * 1.2) + 1024)
         return match_finalize(relaunched, sort=sort)
     pairs = pending["out_pairs"][:n]
     if sort:
@@ -325,8 +372,8 @@ _FINDINGS_BLOCK = 256  # bitmap words per block (FA_BLOCK, csrc/findings.hip)
 def assemble_findings(pending: dict, layout: dict, pkg_base: int, workspace: dict) -> dict:
     """Dedup-match pairs -> the canonical finding stream, without a sort.
 
-    Takes the pending handle of a :func:`match_launch` over the DISTINCT rows
-    of ``layout`` (``run_off``, ``perm2``, ``row_of``) and returns, equal to
+    Takes the pending handle of a :func:`match_launch` or
+    :func:`match_by_window_launch` over the DISTINCT rows of ``layout`` (``run_off``, ``perm2``, ``row_of``) and returns, equal to
     ``expand_dedup_matches`` + ``unique_consecutive`` + ``searchsorted``:
 
       pkg_idx, win_idx   int64 [F], sorted by (pkg << 32 | win)
@@ -336,8 +383,8 @@ def assemble_findings(pending: dict, layout: dict, pkg_base: int, workspace: dic
       uniq_pkgs32        int32 [NU], the same (abom_blast_counts input)
 
     One host read (findings, unique packages, match count) sizes the outputs.
-    On capacity overflow the match is relaunched with a grown buffer, as in
-    :func:`match_finalize`.  ``workspace`` persists between calls and is
+    On capacity overflow the handle relaunches its match with a grown buffer,
+    as in :func:`match_finalize`.  ``workspace`` persists between calls and is
     all-zero outside a call; a call that did not finish leaves it flagged and
     the next call clears it in full.
     """
@@ -379,8 +426,7 @@ def assemble_findings(pending: dict, layout: dict, pkg_base: int, workspace: dic
     if n < 0:
         raise RuntimeError("match: device match count overflowed int32; shard the package batch")
     if n > cap:
-        relaunched = match_launch(*pending["args"], capacity=int(n * 1.2) + 1024,
-                                  **pending.get("kw", {}))
+        relaunched = pending["relaunch"](int(n * 1.2) + 1024)
         return assemble_findings(relaunched, layout, pkg_base, ws)
     if F >= 1 << 31:
         raise RuntimeError(f"assemble_findings: {F} findings exceed int32; shard the package batch")
