@@ -455,6 +455,12 @@ class EstateEngine:
 
         self.agent_ids = torch.arange(estate.n_agents, dtype=torch.int32, device=dev)
         self._bfs_ws: dict = {}
+        # out-degree sum of the BFS sources: a property of the CSR and the
+        # agent ids, like pkg_win_range, so the reach BFS need not read it
+        # back from the device every step
+        agents = self.agent_ids.to(torch.int64)
+        self._agents_degree = int(
+            (self.fwd["row_off"][agents + 1] - self.fwd["row_off"][agents]).sum())
         self._findings_ws: dict = {}  # ops/csrc/findings.hip workspace
         self._match_stream = None  # side stream: match ∥ reach BFS overlap
 
@@ -533,8 +539,17 @@ class EstateEngine:
         packed, _ = self.torch.sort(packed)
         return (packed >> 32), (packed & 0xFFFFFFFF)
 
-    def dependency_reach(self):
-        """u32 hop distance from the nearest agent, per node (multi-source BFS)."""
+    def _reach_begin(self):
+        """Enqueue the reach BFS's dist fill and seeding (no sync); follow
+        with ``dependency_reach(begun=True)`` on the same stream."""
+        from agentbom_amd.ops import native
+
+        native.bfs_begin(self.fwd["row_off"], self.agent_ids, self.N, self._bfs_ws)
+
+    def dependency_reach(self, begun: bool = False):
+        """u32 hop distance from the nearest agent, per node (multi-source BFS).
+
+        ``begun``: :meth:`_reach_begin` has been called for this pass."""
         mask = (1 << ET_USES) | (1 << ET_CONTAINS) | (1 << ET_HAS_CRED) | (1 << ET_PROVIDES_TOOL)
         if self.use_gpu:
             from agentbom_amd.ops import native
@@ -543,6 +558,7 @@ class EstateEngine:
                 self.fwd["row_off"], self.fwd["col"], self.agent_ids, self.N,
                 etype=self.fwd["etype"], allowed_mask=mask, workspace=self._bfs_ws,
                 edge_src=self.fwd["src"], rev=self.rev,
+                begun=begun, sources_degree=self._agents_degree,
             )
         from agentbom_amd.ops import cpu_ref
 
@@ -707,6 +723,11 @@ class EstateEngine:
             if self._match_stream is None:
                 self._match_stream = torch.cuda.Stream(device=self.device)
             side = self._match_stream
+            if reach_dist is None:
+                # the BFS's 4N-byte dist fill and its seeding go ahead of the
+                # match: beside it the fill gets no wave slots (the match
+                # grid holds all of them) and runs at a few % of bandwidth
+                self._reach_begin()
             side.wait_stream(torch.cuda.current_stream())
             dd = self.match_dedup
             with torch.cuda.stream(side):
@@ -731,7 +752,8 @@ class EstateEngine:
                         self.pkg_key_lo_sorted, self.pkg_flags_sorted,
                         self.arena["group_keys"], self.arena["group_off"],
                         self.arena["windows"], pkg_win_range=self.pkg_win_range)
-            dist = reach_dist if reach_dist is not None else self.dependency_reach()
+            dist = (reach_dist if reach_dist is not None
+                    else self.dependency_reach(begun=True))
             torch.cuda.current_stream().wait_stream(side)
             if dd is not None and findings_native_enabled():
                 # pairs -> sorted findings + unique packages + positions in

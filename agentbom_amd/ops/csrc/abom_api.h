@@ -37,7 +37,8 @@ int abom_match_by_window(
     const void* s_key, const void* s_row,
     void* out_pairs, void* out_count, long long capacity, void* stream);
 
-// bfs.hip (abom_bfs_run returns the number of levels run or a negated hipError_t)
+// bfs.hip (abom_bfs_run and abom_bfs_run_ex return the number of levels run
+// or a negated hipError_t)
 int abom_bfs_expand(
     const void* row_off, const void* col, const void* etype, unsigned int allowed_mask,
     const void* frontier, long long frontier_size, void* dist, unsigned int next_level,
@@ -59,6 +60,20 @@ int abom_bfs_run(
     void* frontier_a, void* frontier_b, void* heavy_queue, void* counters,
     int max_levels, const void* edge_src, long long num_edges, double avg_degree,
     const void* rev_off, const void* rev_col, const void* rev_et, void* stream);
+// abom_bfs_begin enqueues the dist fill, the counter zeroing and the seeding
+// without a sync; abom_bfs_run_ex runs the levels (and the begin part unless
+// begun != 0).  sources_degree < 0: read the sources' degree sum from the
+// device; host_counters: pinned host u32[4] for the count reads, nullable
+int abom_bfs_begin(
+    const void* row_off, const void* sources, long long n_sources, void* dist,
+    long long num_nodes, void* frontier_a, void* counters, void* stream);
+int abom_bfs_run_ex(
+    const void* row_off, const void* col, const void* etype, unsigned int allowed_mask,
+    const void* sources, long long n_sources, void* dist, long long num_nodes,
+    void* frontier_a, void* frontier_b, void* heavy_queue, void* counters,
+    int max_levels, const void* edge_src, long long num_edges,
+    const void* rev_off, const void* rev_col, const void* rev_et,
+    int begun, long long sources_degree, void* host_counters, void* stream);
 
 // query.hip
 int abom_impact_query(

@@ -18,9 +18,23 @@
 //   expanded by whole waves from a secondary queue filled in pass 1.
 // - dense levels (frontier edges > 1/8 of all edges) switch to a pass over
 //   all edges or, with a reverse CSR, a bottom-up pass over all vertices.
+// - a block of bfs_expand_kernel or bfs_expand_heavy_kernel stages its claims
+//   in an LDS queue and reserves their slots of the next frontier with ONE
+//   atomic per flush: the frontier counter is a single word, and a returning
+//   atomic per wave and edge-loop iteration ran both kernels at that word's
+//   atomic rate (208 -> 52 us and 40 -> 22 us at 550k edges).
+// - a bottom-up pass also counts the vertices it leaves unvisited that have
+//   an allowed in-edge; when there is none, no later level can claim
+//   anything and the loop ends without a pass that only finds that out.
+// - dist is initialised by a 16-byte-store fill kernel that also zeroes the
+//   counters.  abom_bfs_begin enqueues fill + seed without a sync, so a
+//   caller that overlaps the BFS with other work can put the 4N-byte fill
+//   ahead of that work instead of beside it.
 //
-// The host-side level loop is abom_bfs_run at the end of this file (C++, one
-// sync per level).
+// The host-side level loop is abom_bfs_run_ex at the end of this file (C++,
+// one sync per level, counts read into pinned host memory when the caller
+// passes some; the degree sum of the sources is read only when the caller
+// does not know it).
 
 #include "abom_api.h"
 #include "abom_common.h"
@@ -29,7 +43,13 @@ namespace abom {
 
 // Slots of the device counter array shared by the kernels and the level loop
 // (mirrored in ops/native.py).
-enum { CTR_NEXT = 0, CTR_HEAVY = 1, CTR_DEGREE = 2, CTR_SLOTS = 3 };
+// CTR_OPEN: vertices a bottom-up pass left unvisited that have an allowed
+// in-edge (zero => the BFS is over).
+enum { CTR_NEXT = 0, CTR_HEAVY = 1, CTR_DEGREE = 2, CTR_OPEN = 3, CTR_SLOTS = 4 };
+
+// Entries of the per-block LDS claim queue of bfs_expand_kernel and
+// bfs_expand_heavy_kernel (16 KiB).
+constexpr unsigned BFS_STAGE = 4096;
 
 // One atomic per wave: lanes accumulate locally, reduce, lane 0 adds.
 __device__ __forceinline__ void wave_add_degree(unsigned int* dst, unsigned v) {
@@ -52,9 +72,59 @@ __device__ __forceinline__ unsigned claim_and_append(
     return (unsigned)(row_off[v + 1] - row_off[v]);
 }
 
+// Per-block LDS claim queue of the two vertex-frontier kernels.  `n` counts
+// the claims since the last flush and may pass BFS_STAGE: the claims past it
+// went straight to next_frontier.
+struct ClaimStage {
+    uint32_t v[BFS_STAGE];
+    unsigned n;
+    unsigned base;  // the block's first slot of next_frontier, set by the flush
+};
+
+// claim_and_append with the append staged: the slot comes from an LDS atomic,
+// and only a claim that finds the queue full pays the global one.
+__device__ __forceinline__ unsigned claim_and_stage(
+    uint32_t v, uint32_t level, uint32_t* __restrict__ dist,
+    const uint64_t* __restrict__ row_off, ClaimStage& st,
+    uint32_t* __restrict__ next_frontier, unsigned int* __restrict__ next_count,
+    long long capacity) {
+    if (dist[v] != ABOM_UNVISITED ||
+        atomicCAS(&dist[v], ABOM_UNVISITED, level) != ABOM_UNVISITED)
+        return 0;
+    const unsigned slot = atomicAdd(&st.n, 1u);
+    if (slot < BFS_STAGE) {
+        st.v[slot] = v;
+    } else {
+        const unsigned idx = atomicAdd(next_count, 1u);
+        if ((long long)idx < capacity) next_frontier[idx] = v;
+    }
+    return (unsigned)(row_off[v + 1] - row_off[v]);
+}
+
+// Whole block: reserve the queue's slots of next_frontier with ONE atomic and
+// copy it out coalesced.  Barriers inside; the caller empties the queue
+// (st.n = 0, then a barrier) before the next claim.
+__device__ __forceinline__ void stage_flush(
+    ClaimStage& st, uint32_t* __restrict__ next_frontier,
+    unsigned int* __restrict__ next_count, long long capacity) {
+    __syncthreads();
+    const unsigned n = st.n < BFS_STAGE ? st.n : BFS_STAGE;
+    if (threadIdx.x == 0 && n) st.base = atomicAdd(next_count, n);
+    __syncthreads();
+    if (n) {
+        const unsigned base = st.base;
+        for (unsigned k = threadIdx.x; k < n; k += blockDim.x) {
+            const unsigned idx = base + k;
+            if ((long long)idx < capacity) next_frontier[idx] = st.v[k];
+        }
+    }
+}
+
 // Pass over the frontier: expand vertices with degree < WAVE_DEG inline;
-// defer heavy vertices to the heavy queue.
-__global__ void bfs_expand_kernel(
+// defer heavy vertices to the heavy queue.  Claims are staged in the LDS
+// queue and flushed at the end of each grid-stride round; the round count is
+// block-uniform (from frontier_size), so the barriers are legal.
+__global__ __launch_bounds__(256) void bfs_expand_kernel(
     const uint64_t* __restrict__ row_off,   // [N+1]
     const uint32_t* __restrict__ col,       // [E]
     const uint8_t* __restrict__ etype,      // [E] or nullptr
@@ -70,29 +140,44 @@ __global__ void bfs_expand_kernel(
     unsigned int* __restrict__ next_degree_sum,
     long long capacity) {
     constexpr uint64_t WAVE_DEG = 64;
+    __shared__ ClaimStage st;
+    __shared__ unsigned block_deg;
     const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long rounds = (frontier_size + stride - 1) / stride;
+    if (threadIdx.x == 0) block_deg = 0;
     unsigned my_deg = 0;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < frontier_size;
-         i += stride) {
-        const uint32_t u = frontier[i];
-        const uint64_t beg = row_off[u];
-        const uint64_t end = row_off[u + 1];
-        if (end - beg >= WAVE_DEG) {
-            heavy_queue[atomicAdd(heavy_count, 1u)] = u;
-            continue;
+    for (long long r = 0; r < rounds; ++r) {
+        if (threadIdx.x == 0) st.n = 0;
+        __syncthreads();
+        const long long i = r * stride + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i < frontier_size) {
+            const uint32_t u = frontier[i];
+            const uint64_t beg = row_off[u];
+            const uint64_t end = row_off[u + 1];
+            if (end - beg >= WAVE_DEG) {
+                heavy_queue[atomicAdd(heavy_count, 1u)] = u;
+            } else {
+                for (uint64_t e = beg; e < end; ++e) {
+                    if (edge_filtered(etype, allowed_mask, e)) continue;
+                    my_deg += claim_and_stage(col[e], next_level, dist, row_off, st,
+                                              next_frontier, next_count, capacity);
+                }
+            }
         }
-        for (uint64_t e = beg; e < end; ++e) {
-            if (edge_filtered(etype, allowed_mask, e)) continue;
-            my_deg += claim_and_append(col[e], next_level, dist, row_off, next_frontier,
-                                       next_count, capacity);
-        }
+        stage_flush(st, next_frontier, next_count, capacity);
     }
-    wave_add_degree(next_degree_sum, my_deg);
+    // degree sum: wave reduce, one LDS atomic per wave, one global per block
+    for (int off = 32; off > 0; off >>= 1) my_deg += __shfl_down(my_deg, off, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0 && my_deg) atomicAdd(&block_deg, my_deg);
+    __syncthreads();
+    if (threadIdx.x == 0 && block_deg) atomicAdd(next_degree_sum, block_deg);
 }
 
 // Wave-cooperative expansion of heavy vertices: one wave (64 lanes) walks one
-// vertex's adjacency with coalesced col[] reads.
-__global__ void bfs_expand_heavy_kernel(
+// vertex's adjacency with coalesced col[] reads.  The block's claims share
+// one LDS queue, flushed once when all its waves are done.
+__global__ __launch_bounds__(256) void bfs_expand_heavy_kernel(
     const uint64_t* __restrict__ row_off,
     const uint32_t* __restrict__ col,
     const uint8_t* __restrict__ etype,
@@ -105,10 +190,15 @@ __global__ void bfs_expand_heavy_kernel(
     unsigned int* __restrict__ next_count,
     unsigned int* __restrict__ next_degree_sum,
     long long capacity) {
+    __shared__ ClaimStage st;
     const unsigned heavy_size = *heavy_size_ptr;
     const int lane = threadIdx.x & 63;
     const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
+    // the block's first wave id: no wave of the block has work past the queue
+    if (((long long)blockIdx.x * blockDim.x >> 6) >= heavy_size) return;
+    if (threadIdx.x == 0) st.n = 0;
+    __syncthreads();
     unsigned my_deg = 0;
     for (long long q = wave; q < heavy_size; q += nwaves) {
         const uint32_t u = heavy_queue[q];
@@ -116,10 +206,11 @@ __global__ void bfs_expand_heavy_kernel(
         const uint64_t end = row_off[u + 1];
         for (uint64_t e = beg + lane; e < end; e += 64) {
             if (edge_filtered(etype, allowed_mask, e)) continue;
-            my_deg += claim_and_append(col[e], next_level, dist, row_off, next_frontier,
-                                       next_count, capacity);
+            my_deg += claim_and_stage(col[e], next_level, dist, row_off, st, next_frontier,
+                                      next_count, capacity);
         }
     }
+    stage_flush(st, next_frontier, next_count, capacity);
     wave_add_degree(next_degree_sum, my_deg);
 }
 
@@ -183,24 +274,31 @@ __global__ void bfs_bottom_up_kernel(
     long long num_nodes,
     uint32_t* __restrict__ dist,
     uint32_t cur_level,
-    unsigned int* __restrict__ next_count) {
+    unsigned int* __restrict__ next_count,
+    unsigned int* __restrict__ open_count) {
     const long long stride = (long long)gridDim.x * blockDim.x;
     unsigned my_claims = 0;
+    unsigned my_open = 0;  // left unvisited, yet with an allowed in-edge
     for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < num_nodes;
          v += stride) {
         if (dist[v] != ABOM_UNVISITED) continue;
         const uint64_t beg = rev_off[v];
         const uint64_t end = rev_off[v + 1];
+        bool allowed_edge = false, claimed = false;
         for (uint64_t e = beg; e < end; ++e) {
             if (edge_filtered(rev_et, allowed_mask, e)) continue;
+            allowed_edge = true;
             if (dist[rev_col[e]] == cur_level) {
                 dist[v] = cur_level + 1;
-                ++my_claims;
+                claimed = true;
                 break;
             }
         }
+        my_claims += claimed;
+        my_open += allowed_edge && !claimed;
     }
     wave_add_degree(next_count, my_claims);
+    wave_add_degree(open_count, my_open);
 }
 
 // Rebuild a frontier from dist (nodes claimed at `level`): used when
@@ -241,13 +339,37 @@ __global__ void seed_sources_kernel(
     wave_add_degree(degree_sum, my_deg);
 }
 
+// dist[0..n) = UNVISITED with 16-byte stores, counters = 0.  `head` elements
+// come before the first 16-byte boundary of dist and `n4` whole uint4 follow
+// it; the elements before and after those go out as single words.
+__global__ void bfs_fill_kernel(uint32_t* __restrict__ dist, long long n, long long head,
+                                long long n4, unsigned int* __restrict__ counters) {
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    uint4* __restrict__ body = reinterpret_cast<uint4*>(dist + head);
+    const uint4 fill = make_uint4(ABOM_UNVISITED, ABOM_UNVISITED, ABOM_UNVISITED,
+                                  ABOM_UNVISITED);
+    for (long long i = tid; i < n4; i += stride) body[i] = fill;
+    const long long tail = head + 4 * n4;  // first element after the body
+    if (tid < head) dist[tid] = ABOM_UNVISITED;
+    if (tid < n - tail) dist[tail + tid] = ABOM_UNVISITED;
+    if (tid < CTR_SLOTS) counters[tid] = 0;
+}
+
 // ── Host helpers of the level loop ─────────────────────────────────────────
 
-static int bfs_init(void* dist, long long n, hipStream_t s) {
-    // ABOM_UNVISITED is 0xFFFFFFFF — a byte-uniform pattern, so the DMA
-    // memset path beats a grid-stride store kernel (and frees the CUs for
-    // the match kernel running concurrently on the side stream).
-    return (int)hipMemsetAsync(dist, 0xFF, (size_t)n * sizeof(uint32_t), s);
+// Fill dist and zero the counters in one launch.  The fill used to be a
+// hipMemsetAsync, which the runtime ran as a 256-block kernel at 3 % of the
+// achievable store bandwidth beside the match kernel.
+static int bfs_init(void* dist, long long n, unsigned int* ctr, hipStream_t s) {
+    long long head = (long long)(((16 - ((uintptr_t)dist & 15)) & 15) / sizeof(uint32_t));
+    if (head > n) head = n;
+    const long long n4 = (n - head) / 4;
+    const int block = 256;
+    // head, tail and counters take at most CTR_SLOTS threads: one block has them
+    hipLaunchKernelGGL(bfs_fill_kernel, dim3(grid_for(n4, block)), dim3(block), 0, s,
+                       (uint32_t*)dist, n, head, n4, ctr);
+    return (int)hipGetLastError();
 }
 
 static int bfs_seed(const void* sources, long long n_sources, const void* row_off, void* dist,
@@ -334,7 +456,23 @@ extern "C" int abom_bfs_expand_edges(
     return (int)hipGetLastError();
 }
 
+
 // ── C ABI: the level loop ──────────────────────────────────────────────────
+
+// First part of a BFS, enqueued without a sync: dist = UNVISITED, counters
+// = 0, sources seeded into frontier_a (their degree sum lands in the
+// counters).  abom_bfs_run_ex(..., begun = 1, ...) on the same buffers and
+// stream runs the levels.
+extern "C" int abom_bfs_begin(
+    const void* row_off, const void* sources, long long n_sources, void* dist,
+    long long num_nodes, void* frontier_a, void* counters, void* stream) {
+    using namespace abom;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned int* ctr = (unsigned int*)counters;
+    int rc = bfs_init(dist, num_nodes, ctr, s);
+    if (rc) return rc;
+    return bfs_seed(sources, n_sources, row_off, dist, frontier_a, ctr + CTR_DEGREE, s);
+}
 
 // Full multi-source BFS: host-side level loop, one device->host count read
 // per level.  dist must be u32[N]; frontier_a/b u32[N]; heavy_queue u32[N];
@@ -342,26 +480,39 @@ extern "C" int abom_bfs_expand_edges(
 // array, col-aligned) may be null; when present, levels whose frontier would
 // touch > ~1/8 of all edges go dense: bottom-up over the reverse CSR when
 // rev_off/rev_col are given, else the edge-centric kernel (coalesced
-// streams), instead of per-vertex expansion.
+// streams), instead of per-vertex expansion.  A bottom-up level that leaves
+// no unvisited vertex with an allowed in-edge ends the loop.
+// ``begun`` != 0: abom_bfs_begin has been enqueued on this stream.
+// ``sources_degree``: the degree sum of the sources (duplicates counted), or
+// -1 to read it from the device.  ``host_counters``: pinned host u32
+// [CTR_SLOTS] for the count reads, or null to read into the stack.
 // Returns negative hip error or the number of levels run.
-extern "C" int abom_bfs_run(
+extern "C" int abom_bfs_run_ex(
     const void* row_off, const void* col, const void* etype, unsigned int allowed_mask,
     const void* sources, long long n_sources, void* dist, long long num_nodes,
     void* frontier_a, void* frontier_b, void* heavy_queue, void* counters,
-    int max_levels, const void* edge_src, long long num_edges, double avg_degree,
+    int max_levels, const void* edge_src, long long num_edges,
     const void* rev_off, const void* rev_col, const void* rev_et,
-    void* stream) {
+    int begun, long long sources_degree, void* host_counters, void* stream) {
     using namespace abom;
-    (void)avg_degree;  // part of ABI v1; the mode switches use exact degree sums
     hipStream_t s = (hipStream_t)stream;
     unsigned int* ctr = (unsigned int*)counters;
-    int rc = bfs_init(dist, num_nodes, s);
-    if (rc) return -rc;
-    if ((rc = reset_counters(ctr, s))) return -rc;
-    rc = bfs_seed(sources, n_sources, row_off, dist, frontier_a, ctr + CTR_DEGREE, s);
-    if (rc) return -rc;
+    unsigned int stack_ctr[CTR_SLOTS] = {0, 0, 0, 0};
+    unsigned int* host_ctr = host_counters ? (unsigned int*)host_counters : stack_ctr;
+    int rc;
+    if (!begun) {
+        rc = abom_bfs_begin(row_off, sources, n_sources, dist, num_nodes, frontier_a, counters,
+                            stream);
+        if (rc) return -rc;
+    }
     unsigned int frontier_degree = 0;
-    if ((rc = read_counters(&frontier_degree, ctr + CTR_DEGREE, 1, s))) return -rc;
+    if (sources_degree < 0) {
+        if ((rc = read_counters(host_ctr, ctr + CTR_DEGREE, 1, s))) return -rc;
+        frontier_degree = host_ctr[0];
+    } else {
+        frontier_degree = sources_degree > 0xFFFFFFFFll ? 0xFFFFFFFFu
+                                                        : (unsigned int)sources_degree;
+    }
 
     uint32_t* cur = (uint32_t*)frontier_a;
     uint32_t* nxt = (uint32_t*)frontier_b;
@@ -379,14 +530,16 @@ extern "C" int abom_bfs_run(
         const bool dense = stay_dense ||
                            (edge_src != nullptr && num_edges > 0 &&
                             (double)frontier_degree > (double)num_edges / 8.0);
+        const bool bottom_up = dense && rev_off && rev_col;
         if (dense) {
             stay_dense = true;
-            if (rev_off && rev_col) {
+            if (bottom_up) {
                 hipLaunchKernelGGL(bfs_bottom_up_kernel,
                                    dim3(abom::grid_for(num_nodes, 256)), dim3(256), 0, s,
                                    (const uint64_t*)rev_off, (const uint32_t*)rev_col,
                                    (const uint8_t*)rev_et, allowed_mask, num_nodes,
-                                   (uint32_t*)dist, (unsigned int)(level - 1), ctr + CTR_NEXT);
+                                   (uint32_t*)dist, (unsigned int)(level - 1), ctr + CTR_NEXT,
+                                   ctr + CTR_OPEN);
                 rc = (int)hipGetLastError();
             } else {
                 rc = abom_bfs_expand_edges(edge_src, col, etype, allowed_mask, num_edges,
@@ -405,9 +558,8 @@ extern "C" int abom_bfs_run(
                                    cur, ctr + CTR_NEXT, ctr + CTR_DEGREE, num_nodes);
                 rc = (int)hipGetLastError();
                 if (rc) return -rc;
-                unsigned int rebuilt = 0;
-                if ((rc = read_counters(&rebuilt, ctr + CTR_NEXT, 1, s))) return -rc;
-                frontier_size = rebuilt;
+                if ((rc = read_counters(host_ctr, ctr + CTR_NEXT, 1, s))) return -rc;
+                frontier_size = host_ctr[0];
                 // reset all counters: the rebuilt frontier's degree sum is
                 // the CURRENT level's, while the dense decision needs the
                 // NEXT frontier's (accumulated by the expand below)
@@ -417,10 +569,12 @@ extern "C" int abom_bfs_run(
                               (unsigned int)level, nxt, ctr, heavy_queue, num_nodes, stream);
             if (rc) return -rc;
         }
-        unsigned int host_ctr[CTR_SLOTS] = {0, 0, 0};
         if ((rc = read_counters(host_ctr, ctr, CTR_SLOTS, s))) return -rc;
         frontier_size = host_ctr[CTR_NEXT];
         frontier_degree = host_ctr[CTR_DEGREE];
+        // a claim needs an unvisited vertex with an allowed in-edge: when the
+        // bottom-up pass left none, every later level would claim nothing
+        if (bottom_up && host_ctr[CTR_OPEN] == 0) frontier_size = 0;
         if (stay_dense && frontier_size > 0 &&
             (double)frontier_size < (double)num_edges / 4096.0) {
             // dense claims have trickled out: hand back to vertex mode next
@@ -431,4 +585,19 @@ extern "C" int abom_bfs_run(
         uint32_t* t = cur; cur = nxt; nxt = t;
     }
     return level;
+}
+
+// The one-shot form of ABI v1: begin + levels, degree sum read from the device.
+extern "C" int abom_bfs_run(
+    const void* row_off, const void* col, const void* etype, unsigned int allowed_mask,
+    const void* sources, long long n_sources, void* dist, long long num_nodes,
+    void* frontier_a, void* frontier_b, void* heavy_queue, void* counters,
+    int max_levels, const void* edge_src, long long num_edges, double avg_degree,
+    const void* rev_off, const void* rev_col, const void* rev_et,
+    void* stream) {
+    (void)avg_degree;  // part of ABI v1; the mode switches use exact degree sums
+    return abom_bfs_run_ex(row_off, col, etype, allowed_mask, sources, n_sources, dist, num_nodes,
+                           frontier_a, frontier_b, heavy_queue, counters, max_levels, edge_src,
+                           num_edges, rev_off, rev_col, rev_et, /*begun=*/0,
+                           /*sources_degree=*/-1, /*host_counters=*/nullptr, stream);
 }

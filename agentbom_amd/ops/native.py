@@ -74,6 +74,18 @@ _SIGNATURES = {
         _i32, _c, _i64, _f64,  # max_levels, edge_src, num_edges, avg_degree
         _c, _c, _c, _c,        # rev_off, rev_col, rev_et, stream
     ], _i32),
+    "abom_bfs_begin": ([
+        _c, _c, _i64, _c,    # row_off, sources, n_sources, dist
+        _i64, _c, _c, _c,    # num_nodes, frontier_a, counters, stream
+    ], _i32),
+    "abom_bfs_run_ex": ([
+        _c, _c, _c, _u32,     # row_off, col, etype, allowed_mask
+        _c, _i64, _c, _i64,   # sources, n_sources, dist, num_nodes
+        _c, _c, _c, _c,       # frontier_a, frontier_b, heavy_queue, counters
+        _i32, _c, _i64,       # max_levels, edge_src, num_edges
+        _c, _c, _c,           # rev_off, rev_col, rev_et
+        _i32, _i64, _c, _c,   # begun, sources_degree, host_counters, stream
+    ], _i32),
     "abom_impact_query": ([
         _c, _c, _c, _u32,      # row_off, col, etype, allowed_mask
         _c, _i32, _i32, _i32,  # query_sources, num_queries, max_hops, max_nodes_per_query
@@ -161,7 +173,8 @@ _SIGNATURES = {
 }
 
 # Byte offsets into the BFS ``counters`` buffer (u32 slots of csrc/bfs.hip)
-_CTR_NEXT, _CTR_HEAVY, _CTR_DEGREE = 0, 4, 8
+_CTR_NEXT, _CTR_HEAVY, _CTR_DEGREE, _CTR_OPEN = 0, 4, 8, 12
+_CTR_SLOTS = 4
 
 # Rows with at least this many scanned edges get one wave instead of one
 # thread in the centrality kernels (CENTRALITY_HEAVY_DEGREE, csrc/centrality.hip)
@@ -462,46 +475,79 @@ def match(pkg_group_key, pkg_key_hi, pkg_key_lo, pkg_flags, group_keys, group_of
     return match_finalize(pending)
 
 
+def _bfs_buffers(ws: dict, num_nodes: int, dev):
+    """dist, frontier_a, frontier_b, heavy queue and counters of a BFS workspace."""
+    import torch
+
+    return (_buf(ws, "dist", num_nodes, torch.int32, dev),
+            _buf(ws, "frontier_a", num_nodes, torch.int32, dev),
+            _buf(ws, "frontier_b", num_nodes, torch.int32, dev),
+            _buf(ws, "heavy", num_nodes, torch.int32, dev),
+            _buf(ws, "counters", _CTR_SLOTS, torch.int32, dev, zero=True))
+
+
+def bfs_begin(row_off, sources, num_nodes: int, workspace: dict) -> None:
+    """Enqueue the first part of :func:`bfs` on the current stream without
+    syncing: fill ``dist``, zero the counters, seed the sources.  Follow it
+    with ``bfs(..., workspace=workspace, begun=True)`` on the same stream,
+    graph and sources; work enqueued on other streams in between starts after
+    the fill instead of beside it."""
+    lib = load()
+    dist, fa, _fb, _hq, ctr = _bfs_buffers(workspace, num_nodes, row_off.device)
+    rc = lib.abom_bfs_begin(_ptr(row_off), _ptr(sources), sources.numel(), _ptr(dist),
+                            num_nodes, _ptr(fa), _ptr(ctr), _stream())
+    _check(rc, "abom_bfs_begin")
+
+
 def bfs(row_off, col, sources, num_nodes: int, etype=None, allowed_mask: int = 0xFFFFFFFF,
         max_levels: int = 64, workspace: Optional[dict] = None, edge_src=None,
-        rev=None):
+        rev=None, begun: bool = False, sources_degree: Optional[int] = None):
     """Multi-source BFS over CSR; returns u32 dist (UNVISITED = 0xFFFFFFFF).
 
     ``workspace`` may carry preallocated buffers (dist/frontier_a/frontier_b/
-    heavy/counters) to avoid reallocation in steady-state serving.
+    heavy/counters) to avoid reallocation in steady-state serving; it is left
+    holding the number of levels run in ``workspace["levels"]``.
+    ``begun``: :func:`bfs_begin` has been called on this workspace for this
+    call.  ``sources_degree``: the sum of the out-degrees of the entries of
+    ``sources`` (duplicates counted), when the caller knows it; the read of
+    that sum from the device and its sync are then skipped.
     """
     import torch
 
     lib = load()
     dev = row_off.device
     ws = workspace if workspace is not None else {}
-    dist = _buf(ws, "dist", num_nodes, torch.int32, dev)
-    fa = _buf(ws, "frontier_a", num_nodes, torch.int32, dev)
-    fb = _buf(ws, "frontier_b", num_nodes, torch.int32, dev)
-    hq = _buf(ws, "heavy", num_nodes, torch.int32, dev)
-    ctr = _buf(ws, "counters", 4, torch.int32, dev, zero=True)
+    if begun and (workspace is None or "dist" not in workspace):
+        raise ValueError("bfs: begun=True needs the workspace bfs_begin was called on")
+    dist, fa, fb, hq, ctr = _bfs_buffers(ws, num_nodes, dev)
+    host_ctr = ws.get("host_counters")
+    if host_ctr is None:
+        # pinned, so the per-level count read is a direct copy
+        host_ctr = ws["host_counters"] = torch.zeros(
+            _CTR_SLOTS, dtype=torch.int32, pin_memory=True)
 
     et = _ptr(etype) if etype is not None else None
     if os.environ.get("AGENT_BOM_BFS_DENSE", "1") == "0":
         edge_src = None  # A/B toggle: disable edge-centric dense-frontier mode
     es = _ptr(edge_src) if edge_src is not None else None
     num_edges = col.numel()
-    avg_degree = num_edges / max(num_nodes, 1)
     # direction-optimized dense levels: pass the reverse CSR for bottom-up
     rev_off_p = rev_col_p = rev_et_p = None
     if rev is not None and os.environ.get("AGENT_BOM_BFS_BOTTOMUP", "1") != "0":
         rev_off_p = _ptr(rev["row_off"])
         rev_col_p = _ptr(rev["col"])
         rev_et_p = _ptr(rev["etype"]) if rev.get("etype") is not None else None
-    rc = lib.abom_bfs_run(
+    rc = lib.abom_bfs_run_ex(
         _ptr(row_off), _ptr(col), et, allowed_mask,
         _ptr(sources), sources.numel(), _ptr(dist), num_nodes,
         _ptr(fa), _ptr(fb), _ptr(hq), _ptr(ctr), max_levels,
-        es, num_edges, float(avg_degree),
-        rev_off_p, rev_col_p, rev_et_p, _stream(),
+        es, num_edges, rev_off_p, rev_col_p, rev_et_p,
+        1 if begun else 0, -1 if sources_degree is None else int(sources_degree),
+        _ptr(host_ctr), _stream(),
     )
     if rc < 0:
-        _check(-rc, "abom_bfs_run")
+        _check(-rc, "abom_bfs_run_ex")
+    ws["levels"] = rc
     return dist[:num_nodes]
 
 
