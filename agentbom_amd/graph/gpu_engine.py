@@ -11,9 +11,11 @@ construction) and stays resident in HBM3E.  On top of it:
                          thread per advisory window binary-searching the
                          group's rows in a search table built once
                          (``build_match_search_table``,
-                         ``match_by_window_kernel``);
-                         AGENT_BOM_MATCH_BY_WINDOW=0, or an estate without a
-                         dedup layout, keeps the row kernel there
+                         ``match_by_window_tiled_kernel``, which stages the
+                         rows of 256 consecutive windows in LDS;
+                         AGENT_BOM_MATCH_TILED=0 probes global memory
+                         instead); AGENT_BOM_MATCH_BY_WINDOW=0, or an estate
+                         without a dedup layout, keeps the row kernel there
 - ``dependency_reach()`` multi-source BFS from all agents (ops/csrc/bfs.hip)
 - ``blast_counts()``     segmented joins: per-finding distinct agent/cred/
                          tool reach with CWE-impact filtering.  On the GPU
@@ -718,6 +720,9 @@ class EstateEngine:
             # Overlap: the match kernel has no dependency on the reach BFS,
             # so it runs on a side HIP stream while the BFS host loop (which
             # syncs its own stream every level) drives the default stream.
+            # The count phase of the finding assembly follows the match on
+            # that stream; the main stream joins it after the BFS and runs
+            # the emit phase and everything that needs both arms.
             from agentbom_amd.ops import native
 
             if self._match_stream is None:
@@ -752,14 +757,22 @@ class EstateEngine:
                         self.pkg_key_lo_sorted, self.pkg_flags_sorted,
                         self.arena["group_keys"], self.arena["group_off"],
                         self.arena["windows"], pkg_win_range=self.pkg_win_range)
+                counting = None
+                if dd is not None and findings_native_enabled():
+                    # the count phase of the finding assembly needs the
+                    # pairs and not the BFS: it follows the match on the side
+                    # stream, and its totals are on the host by the time the
+                    # BFS host loop returns
+                    counting = native.assemble_findings_begin(
+                        pending, dd, self._findings_ws)
             dist = (reach_dist if reach_dist is not None
                     else self.dependency_reach(begun=True))
             torch.cuda.current_stream().wait_stream(side)
-            if dd is not None and findings_native_enabled():
+            if counting is not None:
                 # pairs -> sorted findings + unique packages + positions in
                 # HIP (ops/csrc/findings.hip): no sort, one host read
-                assembled = native.assemble_findings(
-                    pending, dd, self.estate.pkg_base, self._findings_ws)
+                assembled = native.assemble_findings_finish(
+                    counting, self.estate.pkg_base)
             else:
                 # downstream always re-canonicalizes; skip the pair sort
                 sp, sw = native.match_finalize(pending, sort=False)

@@ -36,6 +36,14 @@ int abom_match_by_window(
     const void* w_rbeg, const void* w_rend, long long num_windows,
     const void* s_key, const void* s_row,
     void* out_pairs, void* out_count, long long capacity, void* stream);
+// the same match, one block per tile of 256 windows with the tile's slice of
+// s_key staged in LDS; same arguments, same pair output
+int abom_match_by_window_tiled(
+    const void* w_intro_hi, const void* w_intro_lo, const void* w_fixed_hi, const void* w_fixed_lo,
+    const void* w_last_hi, const void* w_last_lo, const void* w_flags,
+    const void* w_rbeg, const void* w_rend, long long num_windows,
+    const void* s_key, const void* s_row,
+    void* out_pairs, void* out_count, long long capacity, void* stream);
 
 // bfs.hip (abom_bfs_run and abom_bfs_run_ex return the number of levels run
 // or a negated hipError_t)

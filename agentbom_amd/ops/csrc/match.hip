@@ -19,7 +19,7 @@
 // - packages with unencodable versions are skipped (PF_ENCODABLE off) and
 //   resolved on the host the same way.
 //
-// Two kernels answer the same question, which (row, window) pairs match:
+// Three kernels answer the same question, which (row, window) pairs match:
 //
 // match_kernel: each thread owns one package row: binary-search the sorted
 // group_key array (top of the tree stays L2/L3-resident; skipped when the
@@ -35,11 +35,21 @@
 // the engine (graph/gpu_engine.py::build_match_search_table), make a
 // window's match set a contiguous run of rows: two or three binary searches
 // find its ends, where the row kernel tests every (row, window) pair of the
-// group.  The default of EstateEngine.step whenever the estate has a dedup
-// layout.  Every key-against-bound comparison still happens in the kernel,
-// every step; the table only joins rows to groups by name.
+// group.  Every key-against-bound comparison still happens in the kernel,
+// every step; the table only joins rows to groups by name.  Selected by
+// AGENT_BOM_MATCH_TILED=0.
 //
-// Both append matches through a device atomic cursor as
+// match_by_window_tiled_kernel: the same searches, one block per tile of 256
+// consecutive windows.  Windows are stored group by group and the table's
+// runs follow the groups, so the rows a tile searches are one short
+// contiguous slice of s_key: the block copies up to MT_CAP rows of it into
+// LDS with coalesced 16-byte loads and the searches probe LDS, not global
+// memory (a probe outside the staged slice reads global memory, so nothing
+// rests on the order of the runs).  All of a window's columns are loaded
+// ahead of the flag tests, and a block reserves its pairs with one atomic.
+// The default of EstateEngine.step whenever the estate has a dedup layout.
+//
+// All append matches through a device atomic cursor as
 // (row_idx << 32 | window_idx), in no particular order; the caller sorts the
 // pairs, or hands them to the finding assembly, which needs no order.
 
@@ -262,6 +272,132 @@ __global__ void match_by_window_kernel(
     }
 }
 
+constexpr int MT_TILE = 256;   // windows per block, one per thread
+constexpr int MT_CAP = 1024;   // rows staged per tile: 16 KiB of LDS, ten blocks per CU
+
+// row_bound over a run of which rows [slo, slo + nst) are staged in `tile`;
+// a probe outside them reads s_key.  The unsigned difference also sends a
+// probe below slo to global memory.
+__device__ __forceinline__ uint32_t row_bound_staged(
+    const ulonglong2* tile, uint32_t slo, uint32_t nst,
+    const ulonglong2* __restrict__ s_key, uint32_t lo, uint32_t hi,
+    uint64_t bhi, uint64_t blo, bool after) {
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        const uint32_t at = mid - slo;
+        const ulonglong2 k = at < nst ? tile[at] : s_key[mid];
+        const bool before = after ? !key_lt(bhi, blo, k.x, k.y) : key_lt(k.x, k.y, bhi, blo);
+        if (before) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// One block per tile of MT_TILE consecutive windows, thread t owns window
+// tile * MT_TILE + t.  Same arguments and same pairs as
+// match_by_window_kernel.
+__global__ __launch_bounds__(MT_TILE) void match_by_window_tiled_kernel(
+    const uint64_t* __restrict__ w_intro_hi,      // [W]
+    const uint64_t* __restrict__ w_intro_lo,
+    const uint64_t* __restrict__ w_fixed_hi,
+    const uint64_t* __restrict__ w_fixed_lo,
+    const uint64_t* __restrict__ w_last_hi,
+    const uint64_t* __restrict__ w_last_lo,
+    const uint8_t* __restrict__ w_flags,
+    const uint32_t* __restrict__ w_rbeg,          // [W]
+    const uint32_t* __restrict__ w_rend,          // [W]
+    long long num_windows,
+    const ulonglong2* __restrict__ s_key,         // [R] (hi, lo)
+    const int* __restrict__ s_row,                // [R]
+    uint64_t* __restrict__ out_pairs,             // [capacity]
+    unsigned int* __restrict__ out_count,
+    long long capacity) {
+    __shared__ ulonglong2 tile[MT_CAP];
+    __shared__ uint32_t wave_lo[MT_TILE / 64], wave_hi[MT_TILE / 64], wave_n[MT_TILE / 64];
+    __shared__ unsigned block_base;
+    const int lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * MT_TILE + threadIdx.x;
+
+    // every column of the window at once: nine independent loads, none
+    // behind a flag test
+    uint8_t f = WF_CPU_FALLBACK;
+    uint32_t rbeg = 0, rend = 0;
+    uint64_t ihi = 0, ilo = 0, fhi = 0, flo = 0, lhi = 0, llo = 0;
+    if (w < num_windows) {
+        f = w_flags[w];
+        rbeg = w_rbeg[w]; rend = w_rend[w];
+        ihi = w_intro_hi[w]; ilo = w_intro_lo[w];
+        fhi = w_fixed_hi[w]; flo = w_fixed_lo[w];
+        lhi = w_last_hi[w];  llo = w_last_lo[w];
+    }
+    const bool searches = !(f & (WF_CPU_FALLBACK | WF_UNFIXED_SUPPRESSED)) && rbeg < rend;
+
+    // the tile's row slice: min rbeg .. max rend over the lanes that search
+    uint32_t slo = searches ? rbeg : 0xFFFFFFFFu;
+    uint32_t shi = searches ? rend : 0u;
+    #pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        slo = min(slo, (uint32_t)__shfl_xor((int)slo, off, 64));
+        shi = max(shi, (uint32_t)__shfl_xor((int)shi, off, 64));
+    }
+    if (lane == 0) {
+        wave_lo[threadIdx.x >> 6] = slo;
+        wave_hi[threadIdx.x >> 6] = shi;
+    }
+    __syncthreads();
+    #pragma unroll
+    for (int i = 0; i < MT_TILE / 64; ++i) {
+        slo = min(slo, wave_lo[i]);
+        shi = max(shi, wave_hi[i]);
+    }
+    const uint32_t nst = slo < shi ? min(shi - slo, (uint32_t)MT_CAP) : 0u;
+    for (uint32_t i = threadIdx.x; i < nst; i += MT_TILE) tile[i] = s_key[slo + i];
+    __syncthreads();
+
+    // intro inclusive, fixed exclusive, last inclusive; the end searches
+    // start at `begin`, as in match_by_window_kernel
+    uint32_t n = 0, begin = rbeg;
+    if (searches) {
+        uint32_t end = rend;
+        if (f & WF_HAS_INTRO)
+            begin = row_bound_staged(tile, slo, nst, s_key, rbeg, rend, ihi, ilo, false);
+        if (f & WF_HAS_FIXED)
+            end = row_bound_staged(tile, slo, nst, s_key, begin, end, fhi, flo, false);
+        if (f & WF_HAS_LAST)
+            end = row_bound_staged(tile, slo, nst, s_key, begin, end, lhi, llo, true);
+        if (begin < end) n = end - begin;
+    }
+
+    // one reservation per block: every atomic on out_count is a request to
+    // one address, and those are served one after the other whatever number
+    // of lanes each carries.  Inclusive prefix sum of the run lengths per
+    // wave, the waves' totals through LDS, thread 0 adds the block's total
+    // and hands the base to the others.  The count keeps growing past
+    // capacity (the caller relaunches), the stores do not.
+    uint32_t incl = n;
+    #pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)incl, off, 64);
+        if (lane >= off) incl += up;
+    }
+    if (lane == 63) wave_n[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t total = 0;
+        #pragma unroll
+        for (int i = 0; i < MT_TILE / 64; ++i) total += wave_n[i];
+        block_base = total ? atomicAdd(out_count, total) : 0u;
+    }
+    __syncthreads();
+    uint32_t before = incl - n;
+    for (int i = 0; i < (int)(threadIdx.x >> 6); ++i) before += wave_n[i];
+    const long long base = (long long)block_base + before;
+    for (uint32_t j = 0; j < n; ++j) {
+        if (base + j < capacity) {
+            out_pairs[base + j] = ((uint64_t)(uint32_t)s_row[begin + j] << 32) | (uint64_t)w;
+        }
+    }
+}
+
 }  // namespace abom
 
 namespace abom {
@@ -319,6 +455,30 @@ extern "C" int abom_match_by_window(
     const int grid = abom::grid_for(num_windows, block);
     hipLaunchKernelGGL(abom::match_by_window_kernel, dim3(grid), dim3(block), 0,
                        (hipStream_t)stream,
+                       (const uint64_t*)w_intro_hi, (const uint64_t*)w_intro_lo,
+                       (const uint64_t*)w_fixed_hi, (const uint64_t*)w_fixed_lo,
+                       (const uint64_t*)w_last_hi, (const uint64_t*)w_last_lo,
+                       (const uint8_t*)w_flags,
+                       (const uint32_t*)w_rbeg, (const uint32_t*)w_rend, num_windows,
+                       (const ulonglong2*)s_key, (const int*)s_row,
+                       (uint64_t*)out_pairs, (unsigned int*)out_count, capacity);
+    return (int)hipGetLastError();
+}
+
+extern "C" int abom_match_by_window_tiled(
+    const void* w_intro_hi, const void* w_intro_lo,
+    const void* w_fixed_hi, const void* w_fixed_lo,
+    const void* w_last_hi, const void* w_last_lo,
+    const void* w_flags,
+    const void* w_rbeg, const void* w_rend, long long num_windows,
+    const void* s_key, const void* s_row,
+    void* out_pairs, void* out_count, long long capacity, void* stream) {
+    if (num_windows <= 0) return 0;
+    // one tile per block: the blocks are short and retire as they finish, so
+    // work queued on other streams finds wave slots while the match runs
+    const long long tiles = (num_windows + abom::MT_TILE - 1) / abom::MT_TILE;
+    hipLaunchKernelGGL(abom::match_by_window_tiled_kernel, dim3((unsigned)tiles),
+                       dim3(abom::MT_TILE), 0, (hipStream_t)stream,
                        (const uint64_t*)w_intro_hi, (const uint64_t*)w_intro_lo,
                        (const uint64_t*)w_fixed_hi, (const uint64_t*)w_fixed_lo,
                        (const uint64_t*)w_last_hi, (const uint64_t*)w_last_lo,

@@ -49,6 +49,13 @@ _SIGNATURES = {
         _c, _c,            # s_key, s_row
         _c, _c, _i64, _c,  # out_pairs, out_count, capacity, stream
     ], _i32),
+    "abom_match_by_window_tiled": ([
+        _c, _c, _c, _c,    # w_intro_hi, w_intro_lo, w_fixed_hi, w_fixed_lo
+        _c, _c, _c,        # w_last_hi, w_last_lo, w_flags
+        _c, _c, _i64,      # w_rbeg, w_rend, num_windows
+        _c, _c,            # s_key, s_row
+        _c, _c, _i64, _c,  # out_pairs, out_count, capacity, stream
+    ], _i32),
     "abom_bfs_expand": ([
         _c, _c, _c, _u32,    # row_off, col, etype, allowed_mask
         _c, _i64, _c, _u32,  # frontier, frontier_size, dist, next_level
@@ -312,11 +319,21 @@ def match_launch(pkg_group_key, pkg_key_hi, pkg_key_lo, pkg_flags, group_keys,
                 pkg_win_range=pkg_win_range, order=order)}
 
 
+def match_tiled_enabled() -> bool:
+    """A/B toggle: AGENT_BOM_MATCH_TILED=0 makes :func:`match_by_window_launch`
+    run ``match_by_window_kernel`` (a thread per window probing the search
+    table in global memory) instead of ``match_by_window_tiled_kernel``."""
+    return os.environ.get("AGENT_BOM_MATCH_TILED", "1") != "0"
+
+
 def match_by_window_launch(windows: dict, table: dict,
                            capacity: Optional[int] = None) -> dict:
     """Launch the window-per-thread match on the CURRENT stream without
     syncing: every arena window binary-searches the run of its group in the
-    row search table (``graph.gpu_engine.build_match_search_table``).
+    row search table (``graph.gpu_engine.build_match_search_table``).  By
+    default the block-tiled kernel, which stages each tile's rows in LDS;
+    AGENT_BOM_MATCH_TILED=0 (:func:`match_tiled_enabled`) searches global
+    memory from a grid-stride thread per window instead.
 
     Returns the same pending handle as :func:`match_launch`, for
     :func:`match_finalize` and :func:`assemble_findings`; the pairs carry the
@@ -326,6 +343,7 @@ def match_by_window_launch(windows: dict, table: dict,
     import torch
 
     lib = load()
+    kernel = lib.abom_match_by_window_tiled if match_tiled_enabled() else lib.abom_match_by_window
     flags = windows["flags"]
     W = flags.numel()
     R = table["s_row"].numel()
@@ -337,7 +355,7 @@ def match_by_window_launch(windows: dict, table: dict,
     dev = flags.device
     out_pairs = torch.empty(cap, dtype=torch.int64, device=dev)
     out_count = torch.zeros(1, dtype=torch.int32, device=dev)
-    rc = lib.abom_match_by_window(
+    rc = kernel(
         _ptr(windows["intro_hi"]), _ptr(windows["intro_lo"]),
         _ptr(windows["fixed_hi"]), _ptr(windows["fixed_lo"]),
         _ptr(windows["last_hi"]), _ptr(windows["last_lo"]), _ptr(flags),
@@ -400,42 +418,99 @@ def assemble_findings(pending: dict, layout: dict, pkg_base: int, workspace: dic
     as in :func:`match_finalize`.  ``workspace`` persists between calls and is
     all-zero outside a call; a call that did not finish leaves it flagged and
     the next call clears it in full.
+
+    The call is :func:`assemble_findings_begin` followed by
+    :func:`assemble_findings_finish`; a caller with other work to wait for
+    runs the first on a side stream behind the match and the second later.
     """
+    return assemble_findings_finish(
+        assemble_findings_begin(pending, layout, workspace), pkg_base)
+
+
+def assemble_findings_begin(pending: dict, layout: dict, workspace: dict) -> dict:
+    """The count phase of :func:`assemble_findings`, enqueued on the CURRENT
+    stream without a host read: workspace set-up, ``abom_findings_count`` and
+    a copy of its three totals to pinned host memory.  It needs the match
+    pairs and nothing else.  Returns the state that
+    :func:`assemble_findings_finish` takes; until that call the workspace is
+    flagged dirty."""
     import torch
 
     lib = load()
     pairs, count = pending["out_pairs"], pending["out_count"]
     cap = min(int(pending["cap"]), pairs.numel())
     dev = pairs.device
-    run_off, perm2, row_of = layout["run_off"], layout["perm2"], layout["row_of"]
+    run_off, perm2 = layout["run_off"], layout["perm2"]
     U, P = run_off.numel() - 1, perm2.numel()
+    state = {"pending": pending, "layout": layout, "ws": workspace, "cap": cap, "bufs": None}
     if P == 0 or cap == 0:
-        e64 = [torch.empty(0, dtype=torch.int64, device=dev) for _ in range(5)]
-        return dict(zip(("pkg_idx", "win_idx", "pkg_nodes", "pos", "uniq_pkgs"), e64),
-                    uniq_pkgs32=torch.empty(0, dtype=torch.int32, device=dev))
+        return state
     ws = workspace
+    fresh = []  # allocated in this call, on this stream's pool
+
+    def buf(key, numel, dtype, zero=False):
+        before = ws.get(key)
+        t = _buf(ws, key, numel, dtype, dev, zero=zero)
+        if t is not before:
+            fresh.append(t)
+        return t
+
     W = (P + 63) // 64
     nblocks = (W + _FINDINGS_BLOCK - 1) // _FINDINGS_BLOCK
-    bitmap = _buf(ws, "fa_bitmap", W, torch.int64, dev, zero=True)
-    row_cnt = _buf(ws, "fa_row_cnt", U, torch.int32, dev, zero=True)
-    row_tail = _buf(ws, "fa_row_tail", U, torch.int32, dev, zero=True)
-    chain_prev = _buf(ws, "fa_chain_prev", cap, torch.int32, dev)
-    rank_of = _buf(ws, "fa_rank_of", cap, torch.int32, dev)
-    word_f = _buf(ws, "fa_word_f", W, torch.int32, dev)
-    block_sums = _buf(ws, "fa_block_sums", 2 * nblocks, torch.int64, dev)
-    totals = _buf(ws, "fa_totals", 3, torch.int64, dev)
+    bitmap = buf("fa_bitmap", W, torch.int64, zero=True)
+    row_cnt = buf("fa_row_cnt", U, torch.int32, zero=True)
+    row_tail = buf("fa_row_tail", U, torch.int32, zero=True)
+    chain_prev = buf("fa_chain_prev", cap, torch.int32)
+    rank_of = buf("fa_rank_of", cap, torch.int32)
+    word_f = buf("fa_word_f", W, torch.int32)
+    block_sums = buf("fa_block_sums", 2 * nblocks, torch.int64)
+    totals = buf("fa_totals", 3, torch.int64)
+    if "fa_host_totals" not in ws:
+        # pinned, so the copy below is asynchronous and the read a plain load
+        ws["fa_host_totals"] = torch.zeros(3, dtype=torch.int64, pin_memory=True)
+        ws["fa_counted"] = torch.cuda.Event()
     if ws.get("fa_dirty"):
         bitmap.zero_()
         row_cnt.zero_()
         row_tail.zero_()
     ws["fa_dirty"] = True
     rc = lib.abom_findings_count(
-        _ptr(pairs), _ptr(count), cap, _ptr(run_off), _ptr(perm2), _ptr(row_of), U, P,
+        _ptr(pairs), _ptr(count), cap, _ptr(run_off), _ptr(perm2), _ptr(layout["row_of"]), U, P,
         _ptr(bitmap), _ptr(row_cnt), _ptr(row_tail), _ptr(chain_prev),
         _ptr(rank_of), _ptr(word_f), _ptr(block_sums), _ptr(totals), _stream(),
     )
     _check(rc, "abom_findings_count")
-    F, NU, n = totals.tolist()  # the one host sync of the assembly
+    ws["fa_host_totals"].copy_(totals[:3], non_blocking=True)
+    ws["fa_counted"].record()
+    state.update(bufs=(bitmap, row_cnt, row_tail, chain_prev, rank_of, word_f, block_sums),
+                 fresh=fresh, stream=torch.cuda.current_stream(), U=U, P=P)
+    return state
+
+
+def assemble_findings_finish(state: dict, pkg_base: int) -> dict:
+    """The rest of :func:`assemble_findings`, on the CURRENT stream, which
+    must be ordered behind the stream the begin part ran on (the same stream,
+    or one that has waited for it): read the totals, relaunch the match on
+    overflow, size the outputs and emit them."""
+    import torch
+
+    lib = load()
+    pending, layout, ws, cap = state["pending"], state["layout"], state["ws"], state["cap"]
+    pairs, count = pending["out_pairs"], pending["out_count"]
+    dev = pairs.device
+    if state["bufs"] is None:
+        e64 = [torch.empty(0, dtype=torch.int64, device=dev) for _ in range(5)]
+        return dict(zip(("pkg_idx", "win_idx", "pkg_nodes", "pos", "uniq_pkgs"), e64),
+                    uniq_pkgs32=torch.empty(0, dtype=torch.int32, device=dev))
+    cur = torch.cuda.current_stream()
+    if cur != state["stream"]:
+        # buffers first allocated under the other stream are used here from
+        # now on: tell the allocator, which frees a block to the pool of the
+        # stream it was allocated on
+        for t in state["fresh"]:
+            t.record_stream(cur)
+    ws["fa_counted"].synchronize()  # the one host sync of the assembly
+    F, NU, n = ws["fa_host_totals"].tolist()
     if n < 0:
         raise RuntimeError("match: device match count overflowed int32; shard the package batch")
     if n > cap:
@@ -443,12 +518,14 @@ def assemble_findings(pending: dict, layout: dict, pkg_base: int, workspace: dic
         return assemble_findings(relaunched, layout, pkg_base, ws)
     if F >= 1 << 31:
         raise RuntimeError(f"assemble_findings: {F} findings exceed int32; shard the package batch")
+    U, P = state["U"], state["P"]
+    bitmap, row_cnt, row_tail, chain_prev, rank_of, word_f, block_sums = state["bufs"]
     pkg_idx, win_idx, pkg_nodes, pos = (
         torch.empty(F, dtype=torch.int64, device=dev) for _ in range(4))
     uniq64 = torch.empty(NU, dtype=torch.int64, device=dev)
     uniq32 = torch.empty(NU, dtype=torch.int32, device=dev)
     rc = lib.abom_findings_emit(
-        _ptr(pairs), _ptr(count), cap, _ptr(row_of), U, P,
+        _ptr(pairs), _ptr(count), cap, _ptr(layout["row_of"]), U, P,
         _ptr(bitmap), _ptr(row_cnt), _ptr(row_tail), _ptr(chain_prev),
         _ptr(rank_of), _ptr(word_f), _ptr(block_sums),
         int(pkg_base), F, NU,
