@@ -27,7 +27,12 @@ construction) and stays resident in HBM3E.  On top of it:
                          the CSR rows per package instead
 - ``score()``            GPU risk scoring (reference formula)
 - ``step()``             full findings pipeline: match -> reach -> join ->
-                         score -> rank (the bench.py timed region)
+                         score -> rank (the bench.py timed region).  Match,
+                         finding assembly and blast counts run on a side
+                         stream under the reach BFS, their outputs sized
+                         from the step before and checked on the device
+                         (AGENT_BOM_FINDINGS_AHEAD=0 emits and counts after
+                         the BFS, sized by a host read)
 - ``blast_radius_query()`` batched bounded BFS for p50 query latency /
                          the /v1/graph read path
 - ``pagerank()`` / ``betweenness()`` / ``choke_points()`` centrality on
@@ -334,6 +339,18 @@ def findings_native_enabled() -> bool:
     import os
 
     return os.environ.get("AGENT_BOM_FINDINGS_NATIVE", "1") != "0"
+
+
+def findings_ahead_enabled() -> bool:
+    """A/B toggle: AGENT_BOM_FINDINGS_AHEAD=0 makes ``EstateEngine.step`` run
+    only the count phase of the finding assembly on the side stream and the
+    emit phase and the blast counts after the reach BFS, sized by a host
+    read, instead of running them all on the side stream under the BFS with
+    output sizes predicted from the step before
+    (``native.assemble_findings_begin_ahead``)."""
+    import os
+
+    return os.environ.get("AGENT_BOM_FINDINGS_AHEAD", "1") != "0"
 
 
 def expand_dedup_matches(torch, layout: dict, su, sw):
@@ -650,6 +667,19 @@ class EstateEngine:
                 self.node_is_db_cred, self.node_is_db_tool,
             )
             n_overflow = None
+        return self._blast_counts_resolve(uniq_pkgs, counts, overflow, n_overflow)
+
+    def _blast_counts_resolve(self, uniq_pkgs, counts, overflow, n_overflow,
+                              counts_only: bool = False):
+        """The kernels' counts [n, 6] as the result dict, the overflowed rows
+        recomputed by the exact join.  ``n_overflow``: how many rows the
+        kernels flagged, None when they did not count them.  ``counts_only``:
+        the caller reads nothing but ``counts2d`` (the step, whose host time
+        after the BFS is on the critical path), so the six column views are
+        left out when no row overflowed."""
+        torch = self.torch
+        if n_overflow == 0 and counts_only:
+            return {"uniq_pkgs": uniq_pkgs, "counts2d": counts}
         result = {
             "uniq_pkgs": uniq_pkgs,
             "n_servers": counts[:, 0].to(torch.int32),
@@ -720,9 +750,10 @@ class EstateEngine:
             # Overlap: the match kernel has no dependency on the reach BFS,
             # so it runs on a side HIP stream while the BFS host loop (which
             # syncs its own stream every level) drives the default stream.
-            # The count phase of the finding assembly follows the match on
+            # The finding assembly and the blast counts follow the match on
             # that stream; the main stream joins it after the BFS and runs
-            # the emit phase and everything that needs both arms.
+            # what needs both arms (score, rank) or a size the side arm
+            # could not predict.
             from agentbom_amd.ops import native
 
             if self._match_stream is None:
@@ -758,7 +789,19 @@ class EstateEngine:
                         self.arena["group_keys"], self.arena["group_off"],
                         self.arena["windows"], pkg_win_range=self.pkg_win_range)
                 counting = None
-                if dd is not None and findings_native_enabled():
+                if (dd is not None and findings_native_enabled()
+                        and self.reach_index is not None and blast_index_enabled()
+                        and findings_ahead_enabled()):
+                    # neither the finding assembly nor the blast counts need
+                    # the BFS: with the output sizes of the last step as
+                    # capacities, all of it follows the match on the side
+                    # stream, enqueued by one call before the BFS loop starts
+                    counting = native.assemble_findings_begin_ahead(
+                        pending, dd, self._findings_ws, self.estate.pkg_base,
+                        native.blast_inputs(
+                            self.rev, self.reach_index, ET_CONTAINS,
+                            self.node_is_db_cred, self.node_is_db_tool, self._blast_ws))
+                elif dd is not None and findings_native_enabled():
                     # the count phase of the finding assembly needs the
                     # pairs and not the BFS: it follows the match on the side
                     # stream, and its totals are on the host by the time the
@@ -787,8 +830,16 @@ class EstateEngine:
         if assembled is not None:
             pkg_idx, win_idx = assembled["pkg_idx"], assembled["win_idx"]
             pkg_nodes, pos = assembled["pkg_nodes"], assembled["pos"]
-            counts = self._blast_counts_fused(assembled["uniq_pkgs"],
-                                              assembled["uniq_pkgs32"])
+            if "blast_counts" in assembled:
+                # counted on the side stream with the assembly; only rows
+                # that overflowed an LDS cap are left, for the exact join
+                counts = self._blast_counts_resolve(
+                    assembled["uniq_pkgs"], assembled["blast_counts"],
+                    assembled["blast_overflow"], assembled["blast_n_overflow"],
+                    counts_only=True)
+            else:
+                counts = self._blast_counts_fused(assembled["uniq_pkgs"],
+                                                  assembled["uniq_pkgs32"])
         else:
             pkg_nodes = pkg_idx + self.estate.pkg_base
             counts = self.blast_counts(pkg_nodes)

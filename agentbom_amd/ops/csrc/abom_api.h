@@ -119,6 +119,16 @@ int abom_blast_counts_indexed(
     long long row_base, long long num_rows,
     const void* node_is_db_cred, const void* node_is_db_tool,
     void* queue, void* counters, void* out_counts, void* out_overflow, void* stream);
+// the indexed passes over at most n_cap packages: the count is the device
+// long long n_dev; the counters are also copied to host_counters (pinned u32[2])
+int abom_blast_counts_indexed_sized(
+    const void* pkgs, const void* n_dev, long long n_cap,
+    const void* rev_off, const void* rev_col, const void* rev_et, int et_contains,
+    const void* reach_off, const void* reach_col, const void* reach_db,
+    long long row_base, long long num_rows,
+    const void* node_is_db_cred, const void* node_is_db_tool,
+    void* queue, void* counters, void* host_counters,
+    void* out_counts, void* out_overflow, void* stream);
 
 // paths.hip (edge_weight and node_gate are nullable)
 int abom_path_relax(
@@ -149,6 +159,37 @@ int abom_findings_emit(
     long long pkg_base, long long num_findings, long long num_unique,
     void* out_pkg_idx, void* out_win_idx, void* out_pkg_nodes, void* out_pos,
     void* out_uniq64, void* out_uniq32, void* stream);
+// abom_findings_emit with the sizes read from totals on the device: it emits
+// and resets only if findings <= findings_cap, unique packages <= unique_cap
+// and match count <= capacity, and otherwise leaves workspace and outputs as
+// they are; num_sized (device long long) receives the packages emitted, or 0
+int abom_findings_emit_sized(
+    const void* pairs, const void* count, long long capacity,
+    const void* row_of, long long num_rows, long long num_packages,
+    void* bitmap, void* row_cnt, void* row_tail, const void* chain_prev,
+    const void* rank_of, const void* word_f, const void* block_off,
+    long long pkg_base, const void* totals, long long findings_cap, long long unique_cap,
+    void* num_sized,
+    void* out_pkg_idx, void* out_win_idx, void* out_pkg_nodes, void* out_pos,
+    void* out_uniq64, void* out_uniq32, void* stream);
+// abom_findings_count, totals -> host_totals (pinned i64[3]),
+// abom_findings_emit_sized and abom_blast_counts_indexed_sized over
+// out_uniq32, enqueued by one call
+int abom_findings_ahead(
+    const void* pairs, const void* count, long long capacity,
+    const void* run_off, const void* perm2, const void* row_of,
+    long long num_rows, long long num_packages,
+    void* bitmap, void* row_cnt, void* row_tail, void* chain_prev,
+    void* rank_of, void* word_f, void* block_sums, void* totals, void* host_totals,
+    long long pkg_base, long long findings_cap, long long unique_cap, void* num_sized,
+    void* out_pkg_idx, void* out_win_idx, void* out_pkg_nodes, void* out_pos,
+    void* out_uniq64, void* out_uniq32,
+    const void* rev_off, const void* rev_col, const void* rev_et, int et_contains,
+    const void* reach_off, const void* reach_col, const void* reach_db,
+    long long row_base, long long reach_rows,
+    const void* node_is_db_cred, const void* node_is_db_tool,
+    void* queue, void* counters, void* host_counters,
+    void* out_counts, void* out_overflow, void* stream);
 
 // centrality.hip (abom_pagerank_run returns the number of passes run,
 // abom_brandes_run the deepest BFS level, or a negated hipError_t; the edge

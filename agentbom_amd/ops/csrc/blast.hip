@@ -225,8 +225,10 @@ __device__ __forceinline__ void write_counts(
 // containing server are finished here from the index row alone (no LDS, no
 // set operation); the rest are queued for the wave kernel.  counters[0] is
 // the queue length, counters[1] the number of overflowed rows.
+// `n_dev`, when given, holds the package count (the sized entry point: the
+// host knows only a bound); otherwise the count is `n`.
 __global__ void __launch_bounds__(256) blast_index_fast_kernel(
-    const uint32_t* __restrict__ pkgs, long long n,
+    const uint32_t* __restrict__ pkgs, long long n, const long long* __restrict__ n_dev,
     const uint64_t* __restrict__ rev_off, const uint32_t* __restrict__ rev_col,
     const uint8_t* __restrict__ rev_et, uint8_t et_contains,
     const int4* __restrict__ reach_off, const int2* __restrict__ reach_db,
@@ -236,6 +238,7 @@ __global__ void __launch_bounds__(256) blast_index_fast_kernel(
     const int lane = threadIdx.x & 63;
     const long long stride = (long long)gridDim.x * blockDim.x;
     const long long start = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n_dev) n = *n_dev;
     // wave-uniform trip count: every lane reaches the ballots below
     for (long long base = start - lane; base < n; base += stride) {
         const long long p = base + lane;
@@ -442,7 +445,7 @@ extern "C" int abom_blast_counts_indexed(
     const int block = 256;
     hipLaunchKernelGGL(abom::blast_index_fast_kernel, dim3(abom::grid_for(n, block)),
                        dim3(block), 0, s,
-                       (const uint32_t*)pkgs, n,
+                       (const uint32_t*)pkgs, n, (const long long*)nullptr,
                        (const uint64_t*)rev_off, (const uint32_t*)rev_col,
                        (const uint8_t*)rev_et, (uint8_t)et_contains,
                        (const int4*)reach_off, (const int2*)reach_db,
@@ -463,6 +466,49 @@ extern "C" int abom_blast_counts_indexed(
                        (const uint32_t*)queue, (unsigned int*)counters,
                        (uint32_t*)out_counts, (uint8_t*)out_overflow);
     return (int)hipGetLastError();
+}
+
+// The same two passes over at most `n_cap` packages; the count itself is the
+// device word `n_dev`, which an earlier kernel of the stream writes.  The
+// grids are sized for n_cap and stride.  The counters reach `host_counters`
+// (pinned, two u32) through a copy on the stream; the caller waits for it.
+extern "C" int abom_blast_counts_indexed_sized(
+    const void* pkgs, const void* n_dev, long long n_cap,
+    const void* rev_off, const void* rev_col, const void* rev_et, int et_contains,
+    const void* reach_off, const void* reach_col, const void* reach_db,
+    long long row_base, long long num_rows,
+    const void* node_is_db_cred, const void* node_is_db_tool,
+    void* queue, void* counters, void* host_counters,
+    void* out_counts, void* out_overflow, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    ABOM_CHECK(hipMemsetAsync(counters, 0, 2 * sizeof(unsigned int), s));
+    if (n_cap > 0) {
+        const int block = 256;
+        hipLaunchKernelGGL(abom::blast_index_fast_kernel, dim3(abom::grid_for(n_cap, block)),
+                           dim3(block), 0, s,
+                           (const uint32_t*)pkgs, 0ll, (const long long*)n_dev,
+                           (const uint64_t*)rev_off, (const uint32_t*)rev_col,
+                           (const uint8_t*)rev_et, (uint8_t)et_contains,
+                           (const int4*)reach_off, (const int2*)reach_db,
+                           (uint32_t)row_base, (uint32_t)num_rows,
+                           (uint32_t*)queue, (unsigned int*)counters,
+                           (uint32_t*)out_counts, (uint8_t*)out_overflow);
+        ABOM_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(abom::blast_index_wave_kernel,
+                           dim3(abom::grid_for(n_cap, abom::WAVES_PER_BLOCK)), dim3(block), 0, s,
+                           (const uint32_t*)pkgs,
+                           (const uint64_t*)rev_off, (const uint32_t*)rev_col,
+                           (const uint8_t*)rev_et, (uint8_t)et_contains,
+                           (const int4*)reach_off, (const uint32_t*)reach_col,
+                           (uint32_t)row_base, (uint32_t)num_rows,
+                           (const uint8_t*)node_is_db_cred, (const uint8_t*)node_is_db_tool,
+                           (const uint32_t*)queue, (unsigned int*)counters,
+                           (uint32_t*)out_counts, (uint8_t*)out_overflow);
+        ABOM_CHECK(hipGetLastError());
+    }
+    ABOM_CHECK(hipMemcpyAsync(host_counters, counters, 2 * sizeof(unsigned int),
+                              hipMemcpyDeviceToHost, s));
+    return 0;
 }
 
 extern "C" int abom_blast_counts(

@@ -227,7 +227,9 @@ __global__ __launch_bounds__(FA_BLOCK) void findings_scan_kernel(
     }
 }
 
-__global__ __launch_bounds__(FA_BLOCK) void findings_emit_kernel(
+// The emit step for the block's 256 bitmap words; every thread of the block
+// must reach the call.
+__device__ __forceinline__ void emit_words(
         const uint64_t* __restrict__ pairs, unsigned long long* __restrict__ bitmap,
         long long W, const int* __restrict__ row_of, const int* __restrict__ row_cnt,
         const int* __restrict__ row_tail, const int* __restrict__ chain_prev,
@@ -236,8 +238,8 @@ __global__ __launch_bounds__(FA_BLOCK) void findings_emit_kernel(
         long long F, long long NU,
         long long* __restrict__ out_pkg_idx, long long* __restrict__ out_win_idx,
         long long* __restrict__ out_pkg_nodes, long long* __restrict__ out_pos,
-        long long* __restrict__ out_uniq64, int* __restrict__ out_uniq32) {
-    __shared__ long long lds[2 * FA_WAVES];
+        long long* __restrict__ out_uniq64, int* __restrict__ out_uniq32,
+        long long* lds) {
     const long long w = (long long)blockIdx.x * FA_BLOCK + threadIdx.x;
     unsigned long long bits = w < W ? bitmap[w] : 0ull;
     long long uo = __popcll(bits), fo = w < W ? word_f[w] : 0;
@@ -274,9 +276,73 @@ __global__ __launch_bounds__(FA_BLOCK) void findings_emit_kernel(
     }
 }
 
+__global__ __launch_bounds__(FA_BLOCK) void findings_emit_kernel(
+        const uint64_t* __restrict__ pairs, unsigned long long* __restrict__ bitmap,
+        long long W, const int* __restrict__ row_of, const int* __restrict__ row_cnt,
+        const int* __restrict__ row_tail, const int* __restrict__ chain_prev,
+        const int* __restrict__ rank_of, const unsigned int* __restrict__ word_f,
+        const long long* __restrict__ block_off, long long pkg_base,
+        long long F, long long NU,
+        long long* __restrict__ out_pkg_idx, long long* __restrict__ out_win_idx,
+        long long* __restrict__ out_pkg_nodes, long long* __restrict__ out_pos,
+        long long* __restrict__ out_uniq64, int* __restrict__ out_uniq32) {
+    __shared__ long long lds[2 * FA_WAVES];
+    emit_words(pairs, bitmap, W, row_of, row_cnt, row_tail, chain_prev, rank_of, word_f,
+               block_off, pkg_base, F, NU, out_pkg_idx, out_win_idx, out_pkg_nodes,
+               out_pos, out_uniq64, out_uniq32, lds);
+}
+
+// The grid-uniform condition of the sized variants: the totals of
+// findings_scan_kernel fit the capacities the host chose before it knew them.
+__device__ __forceinline__ bool sized_ok(const long long* __restrict__ totals,
+                                         long long F_cap, long long NU_cap, long long cap) {
+    const long long n = totals[2];
+    return totals[0] <= F_cap && totals[1] <= NU_cap && n >= 0 && n <= cap;
+}
+
+// findings_emit_kernel with F and NU read from `totals`.  When they do not
+// fit the capacities nothing is read or written beyond `num_sized`, which
+// tells the kernels behind this one how many packages were emitted: NU, or 0.
+__global__ __launch_bounds__(FA_BLOCK) void findings_emit_sized_kernel(
+        const uint64_t* __restrict__ pairs, unsigned long long* __restrict__ bitmap,
+        long long W, const int* __restrict__ row_of, const int* __restrict__ row_cnt,
+        const int* __restrict__ row_tail, const int* __restrict__ chain_prev,
+        const int* __restrict__ rank_of, const unsigned int* __restrict__ word_f,
+        const long long* __restrict__ block_off, long long pkg_base,
+        const long long* __restrict__ totals, long long F_cap, long long NU_cap,
+        long long cap, long long* __restrict__ num_sized,
+        long long* __restrict__ out_pkg_idx, long long* __restrict__ out_win_idx,
+        long long* __restrict__ out_pkg_nodes, long long* __restrict__ out_pos,
+        long long* __restrict__ out_uniq64, int* __restrict__ out_uniq32) {
+    __shared__ long long lds[2 * FA_WAVES];
+    const bool ok = sized_ok(totals, F_cap, NU_cap, cap);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *num_sized = ok ? totals[1] : 0;
+    if (!ok) return;
+    emit_words(pairs, bitmap, W, row_of, row_cnt, row_tail, chain_prev, rank_of, word_f,
+               block_off, pkg_base, totals[0], totals[1], out_pkg_idx, out_win_idx,
+               out_pkg_nodes, out_pos, out_uniq64, out_uniq32, lds);
+}
+
 __global__ __launch_bounds__(FA_BLOCK) void findings_reset_kernel(
         const uint64_t* __restrict__ pairs, const int* __restrict__ count, long long cap,
         long long U, int* __restrict__ row_cnt, int* __restrict__ row_tail) {
+    const long long n = pair_count(count, cap);
+    for (long long i = (long long)blockIdx.x * FA_BLOCK + threadIdx.x; i < n;
+         i += (long long)gridDim.x * FA_BLOCK) {
+        const long long u = (long long)(pairs[i] >> 32);
+        if (u < U) {
+            row_cnt[u] = 0;
+            row_tail[u] = 0;
+        }
+    }
+}
+
+// findings_reset_kernel under the same condition as the sized emit
+__global__ __launch_bounds__(FA_BLOCK) void findings_reset_sized_kernel(
+        const uint64_t* __restrict__ pairs, const int* __restrict__ count, long long cap,
+        long long U, const long long* __restrict__ totals, long long F_cap, long long NU_cap,
+        int* __restrict__ row_cnt, int* __restrict__ row_tail) {
+    if (!sized_ok(totals, F_cap, NU_cap, cap)) return;
     const long long n = pair_count(count, cap);
     for (long long i = (long long)blockIdx.x * FA_BLOCK + threadIdx.x; i < n;
          i += (long long)gridDim.x * FA_BLOCK) {
@@ -352,4 +418,74 @@ extern "C" int abom_findings_emit(
                        (const uint64_t*)pairs, (const int*)count, capacity, num_rows,
                        (int*)row_cnt, (int*)row_tail);
     return (int)hipGetLastError();
+}
+
+extern "C" int abom_findings_emit_sized(
+        const void* pairs, const void* count, long long capacity,
+        const void* row_of, long long num_rows, long long num_packages,
+        void* bitmap, void* row_cnt, void* row_tail, const void* chain_prev,
+        const void* rank_of, const void* word_f, const void* block_off,
+        long long pkg_base, const void* totals, long long findings_cap, long long unique_cap,
+        void* num_sized,
+        void* out_pkg_idx, void* out_win_idx, void* out_pkg_nodes, void* out_pos,
+        void* out_uniq64, void* out_uniq32, void* stream) {
+    if (num_packages <= 0 || capacity <= 0 || findings_cap < 0 || unique_cap < 0)
+        return (int)hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    const long long W = (num_packages + 63) / 64;
+    const long long nblocks = word_blocks(num_packages);
+    // F is not known here: the kernel always runs, block 0 writes num_sized
+    hipLaunchKernelGGL(findings_emit_sized_kernel, dim3((unsigned)nblocks), dim3(FA_BLOCK), 0, s,
+                       (const uint64_t*)pairs, (unsigned long long*)bitmap, W,
+                       (const int*)row_of, (const int*)row_cnt, (const int*)row_tail,
+                       (const int*)chain_prev, (const int*)rank_of,
+                       (const unsigned int*)word_f, (const long long*)block_off,
+                       pkg_base, (const long long*)totals, findings_cap, unique_cap,
+                       capacity, (long long*)num_sized,
+                       (long long*)out_pkg_idx, (long long*)out_win_idx,
+                       (long long*)out_pkg_nodes, (long long*)out_pos,
+                       (long long*)out_uniq64, (int*)out_uniq32);
+    hipLaunchKernelGGL(findings_reset_sized_kernel, dim3(abom::grid_for(capacity, FA_BLOCK)),
+                       dim3(FA_BLOCK), 0, s,
+                       (const uint64_t*)pairs, (const int*)count, capacity, num_rows,
+                       (const long long*)totals, findings_cap, unique_cap,
+                       (int*)row_cnt, (int*)row_tail);
+    return (int)hipGetLastError();
+}
+
+// The whole side arm of the step in one call: count phase, totals to the
+// host, sized emit and reset, then the blast counts of the emitted packages
+// with their two counters to the host.  Nothing here waits for the device.
+extern "C" int abom_findings_ahead(
+        const void* pairs, const void* count, long long capacity,
+        const void* run_off, const void* perm2, const void* row_of,
+        long long num_rows, long long num_packages,
+        void* bitmap, void* row_cnt, void* row_tail, void* chain_prev,
+        void* rank_of, void* word_f, void* block_sums, void* totals, void* host_totals,
+        long long pkg_base, long long findings_cap, long long unique_cap, void* num_sized,
+        void* out_pkg_idx, void* out_win_idx, void* out_pkg_nodes, void* out_pos,
+        void* out_uniq64, void* out_uniq32,
+        const void* rev_off, const void* rev_col, const void* rev_et, int et_contains,
+        const void* reach_off, const void* reach_col, const void* reach_db,
+        long long row_base, long long reach_rows,
+        const void* node_is_db_cred, const void* node_is_db_tool,
+        void* queue, void* counters, void* host_counters,
+        void* out_counts, void* out_overflow, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    int rc = abom_findings_count(pairs, count, capacity, run_off, perm2, row_of, num_rows,
+                                 num_packages, bitmap, row_cnt, row_tail, chain_prev,
+                                 rank_of, word_f, block_sums, totals, stream);
+    if (rc) return rc;
+    ABOM_CHECK(hipMemcpyAsync(host_totals, totals, 3 * sizeof(long long),
+                              hipMemcpyDeviceToHost, s));
+    rc = abom_findings_emit_sized(pairs, count, capacity, row_of, num_rows, num_packages,
+                                  bitmap, row_cnt, row_tail, chain_prev, rank_of, word_f,
+                                  block_sums, pkg_base, totals, findings_cap, unique_cap,
+                                  num_sized, out_pkg_idx, out_win_idx, out_pkg_nodes,
+                                  out_pos, out_uniq64, out_uniq32, stream);
+    if (rc) return rc;
+    return abom_blast_counts_indexed_sized(
+        out_uniq32, num_sized, unique_cap, rev_off, rev_col, rev_et, et_contains,
+        reach_off, reach_col, reach_db, row_base, reach_rows, node_is_db_cred,
+        node_is_db_tool, queue, counters, host_counters, out_counts, out_overflow, stream);
 }

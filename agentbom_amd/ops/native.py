@@ -127,6 +127,15 @@ _SIGNATURES = {
         _c, _c,              # node_is_db_cred, node_is_db_tool
         _c, _c, _c, _c, _c,  # queue, counters, out_counts, out_overflow, stream
     ], _i32),
+    "abom_blast_counts_indexed_sized": ([
+        _c, _c, _i64,      # pkgs, n_dev, n_cap
+        _c, _c, _c, _i32,  # rev_off, rev_col, rev_et, et_contains
+        _c, _c, _c,        # reach_off, reach_col, reach_db
+        _i64, _i64,        # row_base, num_rows
+        _c, _c,            # node_is_db_cred, node_is_db_tool
+        _c, _c, _c,        # queue, counters, host_counters
+        _c, _c, _c,        # out_counts, out_overflow, stream
+    ], _i32),
     "abom_path_relax": ([
         _c, _c, _c, _c,  # edge_src, col, etype, edge_weight
         _c, _c, _c, _c,  # cur, nxt, node_boost, etype_boost
@@ -152,6 +161,32 @@ _SIGNATURES = {
         _i64, _i64, _i64,  # pkg_base, num_findings, num_unique
         _c, _c, _c, _c,   # out_pkg_idx, out_win_idx, out_pkg_nodes, out_pos
         _c, _c, _c,       # out_uniq64, out_uniq32, stream
+    ], _i32),
+    "abom_findings_emit_sized": ([
+        _c, _c, _i64,         # pairs, count, capacity
+        _c, _i64, _i64,       # row_of, num_rows, num_packages
+        _c, _c, _c, _c,       # bitmap, row_cnt, row_tail, chain_prev
+        _c, _c, _c,           # rank_of, word_f, block_off
+        _i64, _c, _i64, _i64,  # pkg_base, totals, findings_cap, unique_cap
+        _c,                   # num_sized
+        _c, _c, _c, _c,       # out_pkg_idx, out_win_idx, out_pkg_nodes, out_pos
+        _c, _c, _c,           # out_uniq64, out_uniq32, stream
+    ], _i32),
+    "abom_findings_ahead": ([
+        _c, _c, _i64,          # pairs, count, capacity
+        _c, _c, _c,            # run_off, perm2, row_of
+        _i64, _i64,            # num_rows, num_packages
+        _c, _c, _c, _c,        # bitmap, row_cnt, row_tail, chain_prev
+        _c, _c, _c, _c, _c,    # rank_of, word_f, block_sums, totals, host_totals
+        _i64, _i64, _i64, _c,  # pkg_base, findings_cap, unique_cap, num_sized
+        _c, _c, _c, _c,        # out_pkg_idx, out_win_idx, out_pkg_nodes, out_pos
+        _c, _c,                # out_uniq64, out_uniq32
+        _c, _c, _c, _i32,      # rev_off, rev_col, rev_et, et_contains
+        _c, _c, _c,            # reach_off, reach_col, reach_db
+        _i64, _i64,            # row_base, reach_rows
+        _c, _c,                # node_is_db_cred, node_is_db_tool
+        _c, _c, _c,            # queue, counters, host_counters
+        _c, _c, _c,            # out_counts, out_overflow, stream
     ], _i32),
     "abom_pagerank_run": ([
         _c, _c, _c, _i64,      # rev_off, rev_col, rev_heavy, num_rev_heavy
@@ -427,17 +462,13 @@ def assemble_findings(pending: dict, layout: dict, pkg_base: int, workspace: dic
         assemble_findings_begin(pending, layout, workspace), pkg_base)
 
 
-def assemble_findings_begin(pending: dict, layout: dict, workspace: dict) -> dict:
-    """The count phase of :func:`assemble_findings`, enqueued on the CURRENT
-    stream without a host read: workspace set-up, ``abom_findings_count`` and
-    a copy of its three totals to pinned host memory.  It needs the match
-    pairs and nothing else.  Returns the state that
-    :func:`assemble_findings_finish` takes; until that call the workspace is
-    flagged dirty."""
+def _findings_state(pending: dict, layout: dict, workspace: dict) -> dict:
+    """Workspace set-up shared by the begin variants: the buffers of
+    csrc/findings.hip sized for this match, cleared if the last call did not
+    finish, and flagged dirty.  ``bufs`` is None when there is nothing to do."""
     import torch
 
-    lib = load()
-    pairs, count = pending["out_pairs"], pending["out_count"]
+    pairs = pending["out_pairs"]
     cap = min(int(pending["cap"]), pairs.numel())
     dev = pairs.device
     run_off, perm2 = layout["run_off"], layout["perm2"]
@@ -464,9 +495,10 @@ def assemble_findings_begin(pending: dict, layout: dict, workspace: dict) -> dic
     rank_of = buf("fa_rank_of", cap, torch.int32)
     word_f = buf("fa_word_f", W, torch.int32)
     block_sums = buf("fa_block_sums", 2 * nblocks, torch.int64)
-    totals = buf("fa_totals", 3, torch.int64)
+    # {findings, unique packages, match count} and the sized emit's word
+    totals = buf("fa_totals", 4, torch.int64)
     if "fa_host_totals" not in ws:
-        # pinned, so the copy below is asynchronous and the read a plain load
+        # pinned, so the copy of the totals is asynchronous and the read a plain load
         ws["fa_host_totals"] = torch.zeros(3, dtype=torch.int64, pin_memory=True)
         ws["fa_counted"] = torch.cuda.Event()
     if ws.get("fa_dirty"):
@@ -474,24 +506,164 @@ def assemble_findings_begin(pending: dict, layout: dict, workspace: dict) -> dic
         row_cnt.zero_()
         row_tail.zero_()
     ws["fa_dirty"] = True
+    state.update(bufs=(bitmap, row_cnt, row_tail, chain_prev, rank_of, word_f, block_sums),
+                 totals=totals, fresh=fresh, stream=torch.cuda.current_stream(), U=U, P=P)
+    return state
+
+
+def assemble_findings_begin(pending: dict, layout: dict, workspace: dict) -> dict:
+    """The count phase of :func:`assemble_findings`, enqueued on the CURRENT
+    stream without a host read: workspace set-up, ``abom_findings_count`` and
+    a copy of its three totals to pinned host memory.  It needs the match
+    pairs and nothing else.  Returns the state that
+    :func:`assemble_findings_finish` takes; until that call the workspace is
+    flagged dirty."""
+    lib = load()
+    state = _findings_state(pending, layout, workspace)
+    if state["bufs"] is None:
+        return state
+    ws = workspace
+    pairs, count, cap = pending["out_pairs"], pending["out_count"], state["cap"]
+    bitmap, row_cnt, row_tail, chain_prev, rank_of, word_f, block_sums = state["bufs"]
+    totals = state["totals"]
     rc = lib.abom_findings_count(
-        _ptr(pairs), _ptr(count), cap, _ptr(run_off), _ptr(perm2), _ptr(layout["row_of"]), U, P,
+        _ptr(pairs), _ptr(count), cap, _ptr(layout["run_off"]), _ptr(layout["perm2"]),
+        _ptr(layout["row_of"]), state["U"], state["P"],
         _ptr(bitmap), _ptr(row_cnt), _ptr(row_tail), _ptr(chain_prev),
         _ptr(rank_of), _ptr(word_f), _ptr(block_sums), _ptr(totals), _stream(),
     )
     _check(rc, "abom_findings_count")
     ws["fa_host_totals"].copy_(totals[:3], non_blocking=True)
     ws["fa_counted"].record()
-    state.update(bufs=(bitmap, row_cnt, row_tail, chain_prev, rank_of, word_f, block_sums),
-                 fresh=fresh, stream=torch.cuda.current_stream(), U=U, P=P)
     return state
+
+
+def findings_ahead_capacity(n: int) -> int:
+    """Output capacity :func:`assemble_findings_begin_ahead` allocates for a
+    quantity that was ``n`` in the last finished call: a sixteenth of headroom
+    and 64 elements, so an estate that grows a little between two calls still
+    fits, and one that had nothing still gets room for a first few."""
+    n = max(int(n), 0)
+    return n + (n >> 4) + 64
+
+
+def blast_inputs(rev: dict, index: dict, et_contains: int, node_is_db_cred,
+                 node_is_db_tool, workspace: dict) -> dict:
+    """The arguments of :func:`blast_counts_indexed` other than the packages,
+    bundled for :func:`assemble_findings_begin_ahead`."""
+    return {"rev": rev, "index": index, "et_contains": int(et_contains),
+            "node_is_db_cred": node_is_db_cred, "node_is_db_tool": node_is_db_tool,
+            "ws": workspace}
+
+
+def _blast_host_counters(workspace: dict):
+    import torch
+
+    host = workspace.get("host_counters")
+    if host is None:
+        # pinned: {queued packages, overflowed rows} arrive by an asynchronous copy
+        host = workspace["host_counters"] = torch.zeros(2, dtype=torch.int32, pin_memory=True)
+    return host
+
+
+def assemble_findings_begin_ahead(pending: dict, layout: dict, workspace: dict,
+                                  pkg_base: int, blast: dict) -> dict:
+    """:func:`assemble_findings_begin` that also runs the emit phase and the
+    indexed blast counts of the emitted packages on the CURRENT stream, with
+    no host read, when the workspace holds a prediction of the output sizes
+    (``workspace["fa_ahead_cap"]`` = (findings, unique packages) capacities,
+    stored by every finish of such a state, which also leaves in
+    ``workspace["fa_ahead_hit"]`` whether it could take the arm's outputs).  The outputs are fresh tensors of
+    those capacities; the kernels read the true sizes from the device and do
+    nothing if they do not fit.  One call, ``abom_findings_ahead``, enqueues
+    it all.  Without a prediction only the count phase runs.  Either way
+    :func:`assemble_findings_finish` returns the assembled findings plus
+    ``blast_counts`` [NU, 6], ``blast_overflow`` [NU] and
+    ``blast_n_overflow``, as :func:`blast_counts_indexed` (``blast``:
+    :func:`blast_inputs`) gives for ``uniq_pkgs32``."""
+    import torch
+
+    caps = workspace.get("fa_ahead_cap")
+    if caps is None:
+        state = assemble_findings_begin(pending, layout, workspace)
+        state["ahead"] = {"blast": blast, "caps": None}
+        return state
+    lib = load()
+    state = _findings_state(pending, layout, workspace)
+    state["ahead"] = {"blast": blast, "caps": None}
+    if state["bufs"] is None:
+        return state
+    ws, bws = workspace, blast["ws"]
+    pairs, count, cap = pending["out_pairs"], pending["out_count"], state["cap"]
+    dev = pairs.device
+    F_cap, NU_cap = int(caps[0]), int(caps[1])
+    fresh = state["fresh"]
+    # two allocations, not eight: this runs on the host before the BFS loop
+    # starts, and every call here delays the first BFS level.  The outputs of
+    # one call share the two blocks; those of two calls share nothing.
+    blob64 = torch.empty(4 * F_cap + NU_cap, dtype=torch.int64, device=dev)
+    blob32 = torch.empty(7 * NU_cap + (NU_cap + 3) // 4, dtype=torch.int32, device=dev)
+    out64 = [blob64[k * F_cap:(k + 1) * F_cap] for k in range(4)]
+    uniq64 = blob64[4 * F_cap:]
+    counts, uniq32 = blob32[:6 * NU_cap], blob32[6 * NU_cap:7 * NU_cap]  # 8-byte rows first
+    overflow = blob32[7 * NU_cap:].view(torch.uint8)
+    fresh.extend((blob64, blob32))
+    for key, numel in (("queue", NU_cap), ("counters", 2)):
+        before = bws.get(key)
+        if _buf(bws, key, numel, torch.int32, dev) is not before:
+            fresh.append(bws[key])
+    host_counters = _blast_host_counters(bws)
+    bitmap, row_cnt, row_tail, chain_prev, rank_of, word_f, block_sums = state["bufs"]
+    totals = state["totals"]
+    rev, index = blast["rev"], blast["index"]
+    rc = lib.abom_findings_ahead(
+        _ptr(pairs), _ptr(count), cap,
+        _ptr(layout["run_off"]), _ptr(layout["perm2"]), _ptr(layout["row_of"]),
+        state["U"], state["P"],
+        _ptr(bitmap), _ptr(row_cnt), _ptr(row_tail), _ptr(chain_prev),
+        _ptr(rank_of), _ptr(word_f), _ptr(block_sums), _ptr(totals),
+        _ptr(ws["fa_host_totals"]),
+        int(pkg_base), F_cap, NU_cap, ctypes.c_void_p(totals.data_ptr() + 24),
+        _ptr(out64[0]), _ptr(out64[1]), _ptr(out64[2]), _ptr(out64[3]),
+        _ptr(uniq64), _ptr(uniq32),
+        _ptr(rev["row_off"]), _ptr(rev["col"]), _ptr(rev["etype"]), blast["et_contains"],
+        _ptr(index["reach_off"]), _ptr(index["reach_col"]), _ptr(index["reach_db"]),
+        index["row_base"], index["reach_off"].shape[0],
+        _ptr(blast["node_is_db_cred"]), _ptr(blast["node_is_db_tool"]),
+        _ptr(bws["queue"]), _ptr(bws["counters"]), _ptr(host_counters),
+        _ptr(counts), _ptr(overflow), _stream(),
+    )
+    _check(rc, "abom_findings_ahead")
+    ws["fa_counted"].record()  # behind both host copies
+    state["ahead"].update(caps=(F_cap, NU_cap), outs=(out64, uniq64, uniq32, counts, overflow),
+                          host_counters=host_counters)
+    return state
+
+
+def _finish_ahead(state: dict, out: dict) -> dict:
+    """A finish that did not take the outputs of the ahead arm: blast counts
+    of what the host-sized path assembled, and the next prediction."""
+    ahead = state.get("ahead")
+    if ahead is None:
+        return out
+    b = ahead["blast"]
+    counts, overflow, n_overflow = blast_counts_indexed(
+        out["uniq_pkgs32"], b["rev"], b["index"], b["et_contains"],
+        b["node_is_db_cred"], b["node_is_db_tool"], b["ws"])
+    out.update(blast_counts=counts, blast_overflow=overflow, blast_n_overflow=n_overflow)
+    state["ws"]["fa_ahead_hit"] = False
+    state["ws"]["fa_ahead_cap"] = (findings_ahead_capacity(out["pkg_idx"].numel()),
+                                   findings_ahead_capacity(out["uniq_pkgs"].numel()))
+    return out
 
 
 def assemble_findings_finish(state: dict, pkg_base: int) -> dict:
     """The rest of :func:`assemble_findings`, on the CURRENT stream, which
     must be ordered behind the stream the begin part ran on (the same stream,
     or one that has waited for it): read the totals, relaunch the match on
-    overflow, size the outputs and emit them."""
+    overflow, size the outputs and emit them.  For a state of
+    :func:`assemble_findings_begin_ahead` whose sizes fit the prediction the
+    outputs exist already and nothing is launched."""
     import torch
 
     lib = load()
@@ -500,8 +672,9 @@ def assemble_findings_finish(state: dict, pkg_base: int) -> dict:
     dev = pairs.device
     if state["bufs"] is None:
         e64 = [torch.empty(0, dtype=torch.int64, device=dev) for _ in range(5)]
-        return dict(zip(("pkg_idx", "win_idx", "pkg_nodes", "pos", "uniq_pkgs"), e64),
-                    uniq_pkgs32=torch.empty(0, dtype=torch.int32, device=dev))
+        return _finish_ahead(state, dict(
+            zip(("pkg_idx", "win_idx", "pkg_nodes", "pos", "uniq_pkgs"), e64),
+            uniq_pkgs32=torch.empty(0, dtype=torch.int32, device=dev)))
     cur = torch.cuda.current_stream()
     if cur != state["stream"]:
         # buffers first allocated under the other stream are used here from
@@ -513,9 +686,24 @@ def assemble_findings_finish(state: dict, pkg_base: int) -> dict:
     F, NU, n = ws["fa_host_totals"].tolist()
     if n < 0:
         raise RuntimeError("match: device match count overflowed int32; shard the package batch")
+    ahead = state.get("ahead")
+    if ahead is not None and ahead["caps"] is not None:
+        F_cap, NU_cap = ahead["caps"]
+        if F <= F_cap and NU <= NU_cap and n <= cap:
+            # the condition the kernels evaluated: they emitted, counted and reset
+            out64, uniq64, uniq32, counts, overflow = ahead["outs"]
+            ws["fa_dirty"] = False
+            ws["fa_ahead_hit"] = True
+            ws["fa_ahead_cap"] = (findings_ahead_capacity(F), findings_ahead_capacity(NU))
+            return {"pkg_idx": out64[0][:F], "win_idx": out64[1][:F],
+                    "pkg_nodes": out64[2][:F], "pos": out64[3][:F],
+                    "uniq_pkgs": uniq64[:NU], "uniq_pkgs32": uniq32[:NU],
+                    "blast_counts": counts[:NU * 6].view(NU, 6),
+                    "blast_overflow": overflow[:NU],
+                    "blast_n_overflow": int(ahead["host_counters"][1])}
     if n > cap:
         relaunched = pending["relaunch"](int(n * 1.2) + 1024)
-        return assemble_findings(relaunched, layout, pkg_base, ws)
+        return _finish_ahead(state, assemble_findings(relaunched, layout, pkg_base, ws))
     if F >= 1 << 31:
         raise RuntimeError(f"assemble_findings: {F} findings exceed int32; shard the package batch")
     U, P = state["U"], state["P"]
@@ -534,8 +722,9 @@ def assemble_findings_finish(state: dict, pkg_base: int) -> dict:
     )
     _check(rc, "abom_findings_emit")
     ws["fa_dirty"] = False
-    return {"pkg_idx": pkg_idx, "win_idx": win_idx, "pkg_nodes": pkg_nodes, "pos": pos,
-            "uniq_pkgs": uniq64, "uniq_pkgs32": uniq32}
+    return _finish_ahead(state, {
+        "pkg_idx": pkg_idx, "win_idx": win_idx, "pkg_nodes": pkg_nodes, "pos": pos,
+        "uniq_pkgs": uniq64, "uniq_pkgs32": uniq32})
 
 
 def match(pkg_group_key, pkg_key_hi, pkg_key_lo, pkg_flags, group_keys, group_off,
@@ -781,6 +970,43 @@ def blast_counts_indexed(pkgs, rev, index: dict, et_contains: int,
     _check(rc, "abom_blast_counts_indexed")
     n_overflow = int(counters[1].item())
     return out_counts.view(n, 6), out_overflow, n_overflow
+
+
+def blast_counts_indexed_sized(pkgs, n_dev, rev, index: dict, et_contains: int,
+                               node_is_db_cred, node_is_db_tool, workspace: dict):
+    """:func:`blast_counts_indexed` for a package count that is on the device:
+    ``pkgs`` (int32) is a buffer of some capacity, ``n_dev`` an int64 tensor
+    whose first element says how many of its entries count.  Grids are sized
+    from the capacity; {queued packages, overflowed rows} come back through
+    pinned host memory.  Returns (counts [capacity * 6], overflow
+    [capacity], queued, overflowed rows); rows from ``n_dev`` on are not
+    written.  The step runs the same entry point inside
+    ``abom_findings_ahead``."""
+    import torch
+
+    lib = load()
+    n_cap = pkgs.numel()
+    dev = pkgs.device
+    out_counts = torch.empty(n_cap * 6, dtype=torch.int32, device=dev)
+    out_overflow = torch.empty(n_cap, dtype=torch.uint8, device=dev)
+    queue = _buf(workspace, "queue", n_cap, torch.int32, dev)
+    counters = _buf(workspace, "counters", 2, torch.int32, dev)
+    host = _blast_host_counters(workspace)
+    rc = lib.abom_blast_counts_indexed_sized(
+        _ptr(pkgs), _ptr(n_dev), n_cap,
+        _ptr(rev["row_off"]), _ptr(rev["col"]), _ptr(rev["etype"]), et_contains,
+        _ptr(index["reach_off"]), _ptr(index["reach_col"]), _ptr(index["reach_db"]),
+        index["row_base"], index["reach_off"].shape[0],
+        _ptr(node_is_db_cred), _ptr(node_is_db_tool),
+        _ptr(queue), _ptr(counters), _ptr(host),
+        _ptr(out_counts), _ptr(out_overflow), _stream(),
+    )
+    _check(rc, "abom_blast_counts_indexed_sized")
+    done = torch.cuda.Event()
+    done.record()
+    done.synchronize()
+    queued, n_overflow = host.tolist()
+    return out_counts, out_overflow, queued, n_overflow
 
 
 def risk_weights_array() -> np.ndarray:
