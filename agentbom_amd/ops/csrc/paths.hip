@@ -67,7 +67,12 @@ __global__ void path_relax_kernel(
         if (!(lu0 | lu1)) continue;
         int32_t v = col[e];
         float step = etype_boost[et] + node_boost[v];
-        if (edge_weight) step += edge_weight[e] * 0.3f;
+        if (edge_weight) {
+            // no FMA: the host re-derives this score and compares with ==
+#pragma clang fp contract(off)
+            const float scaled = edge_weight[e] * 0.3f;
+            step = step + scaled;
+        }
         bool gate = etype_gate[et] || (node_gate && node_gate[v]);
         if (lu0) {
             // predecessor-avoidance: never relax straight back to the node

@@ -251,3 +251,154 @@ def test_dp_threshold_switch(monkeypatch):
     routed = ap.compute_fused_attack_paths(graph, max_paths=10)
     dp = ap.compute_attack_paths_dp(graph, max_paths=10)
     assert [p.id for p in routed] == [p.id for p in dp]
+
+
+# ── edge weights: the oracle against an independent scalar relaxation ───────
+
+
+def _scalar_relax(src, dst, et, w, cur, nb, eb, tv, eg, ng):
+    """One hop, edge by edge, in np.float32 scalars (one rounding per
+    operation), keeping a dict of the best (score, edge) per (node, slot).
+    Shares no code with cpu_ref.path_relax."""
+    import struct
+
+    f32 = np.float32
+    no_edge = 0xFFFFFFFF
+    best: dict[tuple[int, int], tuple[float, int]] = {}
+    for e in range(len(src)):
+        t = int(et[e])
+        if not tv[t]:
+            continue
+        u, v = int(src[e]), int(dst[e])
+        for slot in (0, 1):
+            lab = int(cur[u * 2 + slot])
+            if lab == 0:
+                continue
+            pe = lab & no_edge
+            if pe != no_edge and int(src[pe]) == v:
+                continue  # 2-cycle guard
+            bits = (lab >> 32) & 0x7FFFFFFF
+            prev = f32(struct.unpack("<f", struct.pack("<I", bits))[0])
+            step = f32(eb[t]) + f32(nb[v])
+            if w is not None:
+                scaled = f32(w[e]) * f32(0.3)
+                step = step + scaled
+            score = prev + step
+            assert isinstance(score, np.float32)
+            gated = slot == 1 or bool(eg[t]) or (ng is not None and bool(ng[v]))
+            key = (v, 1 if gated else 0)
+            cand = (float(score), e)  # score first, larger edge index on ties
+            if key not in best or cand > best[key]:
+                best[key] = cand
+    out = np.zeros_like(cur)
+    for (v, slot), (score, e) in best.items():
+        bits = struct.unpack("<I", struct.pack("<f", score))[0]
+        out[v * 2 + slot] = np.uint64(((bits | 0x80000000) << 32) | e)
+    return out
+
+
+class TestWeightedOracle:
+    def test_scalar_oracle_matches_cpu_ref_random(self):
+        from path_relax_cases import random_graph, tables
+
+        from agentbom_amd.ops import cpu_ref
+
+        g = random_graph(300, 3000, 16, seed=9001)
+        eb, tv, eg = tables()
+        assert ((g["w"] != 1.0) & (g["w"] != 0.0)).sum() > 1500
+        for ng in (g["ng"], None):
+            a = b = g["cur"]
+            for hop in range(1, 4):
+                a = cpu_ref.path_relax(g["src"], g["dst"], g["et"], g["w"], a,
+                                       g["nb"], eb, tv, eg, ng)
+                b = _scalar_relax(g["src"], g["dst"], g["et"], g["w"], b,
+                                  g["nb"], eb, tv, eg, ng)
+                assert np.array_equal(a, b), f"hop {hop}"
+                assert np.count_nonzero(a) > 20 * hop
+            assert np.count_nonzero(a[0::2]) and np.count_nonzero(a[1::2])
+
+    def test_hand_built_cases(self):
+        from path_relax_cases import NO_EDGE, hand_cases, tables
+
+        from agentbom_amd.ops import cpu_ref
+
+        eb, tv, eg = tables()
+        cases = hand_cases()
+        assert len(cases) == 9
+        for name, c in cases.items():
+            args = (c["src"], c["dst"], c["et"], c["w"], c["cur"], c["nb"],
+                    eb, tv, eg, c["ng"])
+            assert np.array_equal(_scalar_relax(*args), c["expect"]), name
+            assert np.array_equal(cpu_ref.path_relax(*args), c["expect"]), name
+        tie = cases["tie_larger_edge_wins"]["expect"]
+        assert int(tie[2 * 2 + 0]) & NO_EDGE == 1
+
+
+def _dfs_best_weighted(src, dst, et, w, nb, eb, tv, eg, ng, entries, tm,
+                       max_depth):
+    """_dfs_best_per_target with the weight term (float64 throughout)."""
+    from collections import defaultdict
+
+    out_edges = defaultdict(list)
+    for e in range(len(src)):
+        if tv[et[e]]:
+            out_edges[int(src[e])].append(e)
+    best: dict[int, float] = {}
+    for entry in entries:
+        stack = [(int(entry), 0.0, False, frozenset([int(entry)]), 0)]
+        while stack:
+            u, score, gated, visited, depth = stack.pop()
+            if gated and tm[u] and depth > 0:
+                best[u] = max(best.get(u, score), score)
+            if depth >= max_depth:
+                continue
+            for e in out_edges[u]:
+                v = int(dst[e])
+                if v in visited:
+                    continue
+                step = float(eb[et[e]]) + float(nb[v]) + float(w[e]) * 0.3
+                g2 = gated or bool(eg[et[e]]) or (ng is not None and bool(ng[v]))
+                stack.append((v, score + step, g2, visited | {v}, depth + 1))
+    return best
+
+
+@pytest.mark.parametrize("use_node_gate", [True, False],
+                         ids=["node_gate", "no_node_gate"])
+def test_weighted_dp_equals_dfs_and_loses_nothing(use_node_gate):
+    """The acyclic-estate DFS check again, with per-edge weights: every
+    target the DFS reaches by a gated simple path within max_depth has a DP
+    hit, and the best scores agree.
+
+    Tolerance: PathHit.score is round(score, 2), at most 0.005 from the f32
+    score.  The f32 score sums at most 6 hops of 4 roundings each on values
+    below 64, so it is within 24 * 64 * 2**-24 < 1e-4 of the float64 DFS."""
+    from path_relax_cases import random_weights
+
+    est = generate_estate(n_agents=12, n_servers=40, n_packages=400,
+                          name_catalog=100, seed=77)
+    src = est.edge_src.astype(np.int32)
+    dst = est.edge_dst.astype(np.int32)
+    et = est.edge_type
+    eb, tv, eg = _tables({0: 0.3, 1: 0.3, 2: 1.5, 3: 0.3}, [0, 1, 2, 3],
+                         gates=[2])
+    rng = np.random.default_rng(6)
+    nb = (rng.random(est.num_nodes) * 2).astype(np.float32)
+    ng = (rng.random(est.num_nodes) < 0.15).astype(np.uint8) if use_node_gate else None
+    w = random_weights(rng, len(src))
+    tm = np.zeros(est.num_nodes, dtype=np.uint8)
+    tm[est.cred_base:est.cred_base + est.n_creds] = 1
+    tm[est.tool_base:est.tool_base + est.n_tools] = 1
+    entries = np.arange(est.n_agents)
+
+    hits = run_path_dp(src, dst, et, w, est.num_nodes, entries, nb, eb,
+                       tv, eg, ng, tm, max_depth=6, k=10_000)
+    dp_best = {h.target: h.score for h in hits}
+    dfs_best = _dfs_best_weighted(src, dst, et, w, nb, eb, tv, eg, ng,
+                                  entries, tm, 6)
+    assert dfs_best, "the estate must have gated paths"
+    assert set(dp_best) == set(dfs_best), "DP lost (or invented) targets"
+    for t, s in dfs_best.items():
+        assert s < 64.0
+        assert abs(dp_best[t] - s) <= 0.005 + 1e-4, (t, dp_best[t], s)
+    for h in hits:
+        assert len(set(h.nodes)) == len(h.nodes)
