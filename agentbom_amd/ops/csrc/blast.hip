@@ -115,6 +115,13 @@ __device__ __forceinline__ void collect_fwd2(
 
 // Distinct count of lds[0..m): lane-strided first-occurrence scan.
 // Also counts distinct elements whose db_flag[node] is set.
+// FULL_SCAN compares an entry with every earlier one, four per iteration,
+// instead of leaving the loop at the first hit: with the exit every LDS read
+// waits for the compare before it, and the heavy packages of the indexed
+// wave kernel (hundreds of entries) were its tail.  Same counts either way.
+// blast_count_kernel keeps the exit: the wider loop costs it a wave per
+// SIMD, and nothing measured that path.
+template <bool FULL_SCAN>
 __device__ __forceinline__ void distinct_count(
     const uint32_t* lds, int m, const uint8_t* __restrict__ db_flag,
     int lane, int* out_all, int* out_db) {
@@ -122,8 +129,16 @@ __device__ __forceinline__ void distinct_count(
     for (int i = lane; i < m; i += 64) {
         const uint32_t v = lds[i];
         bool first = true;
-        for (int j = 0; j < i; ++j) {
-            if (lds[j] == v) { first = false; break; }
+        if (FULL_SCAN) {
+            int dup = 0, j = 0;
+            for (; j + 4 <= i; j += 4)
+                dup |= (lds[j] == v) | (lds[j + 1] == v) | (lds[j + 2] == v) | (lds[j + 3] == v);
+            for (; j < i; ++j) dup |= lds[j] == v;
+            first = !dup;
+        } else {
+            for (int j = 0; j < i; ++j) {
+                if (lds[j] == v) { first = false; break; }
+            }
         }
         if (first) {
             ++cnt;
@@ -185,10 +200,10 @@ __global__ void __launch_bounds__(256) blast_count_kernel(
         }
 
         int srv_all, srv_db, ag_all, ag_db, cr_all, cr_db, tl_all, tl_db;
-        distinct_count(lds_srv[wid], n_srv, nullptr, lane, &srv_all, &srv_db);
-        distinct_count(lds_ag[wid], n_ag, nullptr, lane, &ag_all, &ag_db);
-        distinct_count(lds_cr[wid], n_cr, node_is_db_cred, lane, &cr_all, &cr_db);
-        distinct_count(lds_tl[wid], n_tl, node_is_db_tool, lane, &tl_all, &tl_db);
+        distinct_count<false>(lds_srv[wid], n_srv, nullptr, lane, &srv_all, &srv_db);
+        distinct_count<false>(lds_ag[wid], n_ag, nullptr, lane, &ag_all, &ag_db);
+        distinct_count<false>(lds_cr[wid], n_cr, node_is_db_cred, lane, &cr_all, &cr_db);
+        distinct_count<false>(lds_tl[wid], n_tl, node_is_db_tool, lane, &tl_all, &tl_db);
 
         if (lane == 0) {
             out_overflow[p] = 0;
@@ -417,9 +432,9 @@ __global__ void __launch_bounds__(256) blast_index_wave_kernel(
         }
 
         int ag_all, ag_db, cr_all, cr_db, tl_all, tl_db;
-        distinct_count(lds_ag[wid], n_ag, nullptr, lane, &ag_all, &ag_db);
-        distinct_count(lds_cr[wid], n_cr, node_is_db_cred, lane, &cr_all, &cr_db);
-        distinct_count(lds_tl[wid], n_tl, node_is_db_tool, lane, &tl_all, &tl_db);
+        distinct_count<true>(lds_ag[wid], n_ag, nullptr, lane, &ag_all, &ag_db);
+        distinct_count<true>(lds_cr[wid], n_cr, node_is_db_cred, lane, &cr_all, &cr_db);
+        distinct_count<true>(lds_tl[wid], n_tl, node_is_db_tool, lane, &tl_all, &tl_db);
 
         if (lane == 0) {
             out_overflow[p] = 0;
