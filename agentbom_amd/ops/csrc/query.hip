@@ -36,6 +36,10 @@ __global__ void impact_query_kernel(
     for (int q = blockIdx.x; q < num_queries; q += gridDim.x) {
         // reset LDS state
         for (int i = threadIdx.x; i < IQ_HASH; i += blockDim.x) h_table[i] = ABOM_UNVISITED;
+        // the seed below lands in a slot that another wave clears: without
+        // this barrier a late clear wipes it, and a cycle back to the source
+        // reports the source a second time
+        __syncthreads();
         if (threadIdx.x == 0) {
             fr_size[0] = 1;
             fr_size[1] = 0;

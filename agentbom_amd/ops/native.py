@@ -893,10 +893,13 @@ def impact_query(row_off, col, query_sources, etype=None, allowed_mask: int = 0x
     Returns (nodes u32 [Q, max_nodes], hops u8 [Q, max_nodes], counts u32 [Q],
     truncated u8 [Q]).  ``out`` may carry those four tensors preallocated; the
     call then allocates nothing and is exactly one kernel launch, which is
-    what a hipGraph capture needs.
+    what a hipGraph capture needs.  Hops are reported as uint8, so
+    ``max_hops`` above 255 is refused.
     """
     import torch
 
+    if max_hops > 255:
+        raise ValueError(f"max_hops {max_hops} does not fit the uint8 hop output (max 255)")
     lib = load()
     dev = row_off.device
     Q = query_sources.numel()

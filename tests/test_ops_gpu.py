@@ -671,16 +671,10 @@ def test_rollup_gpu_matches_cpu(estate, dev):
 def test_rank_kernel_matches_torch_key_sort(dev):
     """Counting-sort rank kernel == the quantized key sort, incl. ties,
     clamping, odd sizes, and all-equal scores."""
+    from score_tail_cases import rank_oracle as oracle
+
     from agentbom_amd.graph.gpu_engine import rank_order
     from agentbom_amd.ops import native
-
-    def oracle(scores_cpu):
-        n = scores_cpu.numel()
-        q = (scores_cpu * 100).round().clamp(0, 1000).to(torch.int64)
-        bits = max(1, (n - 1).bit_length())
-        key = ((1000 - q) << bits) | torch.arange(n)
-        skey, _ = torch.sort(key)
-        return skey & ((1 << bits) - 1)
 
     gen = torch.Generator().manual_seed(7)
     for n in (1, 63, 64, 257, 4096, 100_001, 500_000):
