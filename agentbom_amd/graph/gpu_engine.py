@@ -33,6 +33,14 @@ construction) and stays resident in HBM3E.  On top of it:
                          from the step before and checked on the device
                          (AGENT_BOM_FINDINGS_AHEAD=0 emits and counts after
                          the BFS, sized by a host read)
+- ``transitive_blast()`` / ``step(blast_depth=k)`` multi-hop delegation
+                         expansion over agent<->server sharing: per matched
+                         package the agents first reached at hop 2..5, the
+                         deepest hop and the transitive credentials, from the
+                         reach index and a per-agent server index
+                         (``build_agent_index``) by the two kernels of
+                         ops/csrc/blast_hops.hip; packages that overflow an
+                         LDS cap are recomputed by an exact join
 - ``blast_radius_query()`` batched bounded BFS for p50 query latency /
                          the /v1/graph read path
 - ``pagerank()`` / ``betweenness()`` / ``choke_points()`` centrality on
@@ -51,6 +59,7 @@ from typing import Optional
 
 import numpy as np
 
+from agentbom_amd.models.blast import HOP_RISK_FACTORS
 from agentbom_amd.models.cwe_impact import (
     IMPACT_CODE,
     IMPACT_CREDENTIAL_ACCESS,
@@ -312,6 +321,37 @@ def build_reach_index(torch, src, dst, et, server_base: int, n_servers: int,
     }
 
 
+def build_agent_index(torch, src, dst, et, n_agents: int, reach_index: dict) -> dict:
+    """Per-agent server index for the multi-hop expansion
+    (ops/csrc/blast_hops.hip), the forward counterpart of the agents segment
+    of the reach index and built once with it.  Agents are the node ids
+    ``0..n_agents-1``.  Layout:
+      agent_off  int32 [n_agents+1]: agent -> its span in ``agent_srv``
+      agent_srv  int32 [T]: each agent's distinct servers (USES targets),
+                 strictly ascending by node id
+    The expansion looks servers up in the reach index and agents up here, so
+    every USES edge must run from an agent id to a server with a reach row.
+    """
+    dev = src.device
+    uses = et == ET_USES
+    a, s = src[uses].to(torch.int64), dst[uses].to(torch.int64)
+    lo = int(reach_index["row_base"])
+    hi = lo + int(reach_index["reach_off"].shape[0])
+    if a.numel() and (int(a.max().item()) >= n_agents or int(s.min().item()) < lo
+                      or int(s.max().item()) >= hi):
+        raise ValueError("agent index: a USES edge leaves the agent or server id range")
+    # one key per (agent, server); unique() sorts and deduplicates
+    key = torch.unique((a << 32) | s)
+    if key.numel() >= 2 ** 31:
+        raise ValueError("agent index exceeds int32 offsets")
+    agent_off = torch.zeros(n_agents + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(key >> 32, minlength=n_agents), 0, out=agent_off[1:])
+    return {
+        "agent_off": agent_off.to(torch.int32).contiguous(),
+        "agent_srv": (key & 0xFFFFFFFF).to(torch.int32).contiguous(),
+    }
+
+
 def blast_index_enabled() -> bool:
     """A/B toggle: AGENT_BOM_BLAST_INDEX=0 makes ``_blast_counts_fused`` walk
     the CSR rows per package (``native.blast_counts``) instead of joining
@@ -499,6 +539,13 @@ class EstateEngine:
         self.reach_index = build_reach_index(
             torch, src, dst, et, estate.server_base, estate.n_servers,
             self.node_is_db_cred, self.node_is_db_tool) if self.use_gpu else None
+        # per-agent server index of the multi-hop expansion: same lifetime
+        self._hops_ws: dict = {}
+        self.agent_index = build_agent_index(
+            torch, src, dst, et, estate.n_agents, self.reach_index) if self.use_gpu else None
+        self._hop_factor = torch.tensor(
+            [0.0] + [HOP_RISK_FACTORS[h] for h in range(1, 6)],
+            dtype=torch.float32, device=dev)
 
     def _build_csr(self, src, dst, et):
         """GPU CSR construction: stable sort by src, bincount offsets."""
@@ -743,7 +790,14 @@ class EstateEngine:
 
         ``reach_dist`` overrides the locally-computed dependency-reach
         distances (multi-GPU mode passes the shard's slice of the
-        distributed BFS result)."""
+        distributed BFS result).
+
+        ``blast_depth`` > 1 (clamped to 5) adds the multi-hop delegation
+        expansion per finding: ``hop_depth`` uint8, ``transitive_agents`` and
+        ``transitive_creds`` int32 (see :meth:`transitive_blast`) and
+        ``transitive_scores`` fp32 = ``scores * HOP_RISK_FACTORS[hop_depth]``
+        where ``hop_depth`` > 1, else 0.  At 1 the pass is the same as before
+        and returns no such keys."""
         torch = self.torch
         assembled = None
         if self.use_gpu:
@@ -861,7 +915,7 @@ class EstateEngine:
             scores, n_agents, n_creds, n_tools = self._score_cpu(
                 counts, pos, pkg_nodes, win_idx, dist)
 
-        return {
+        res = {
             "n_findings": int(n_findings),
             "scores": scores,
             # deterministic rank: quantized score desc, finding index asc
@@ -873,6 +927,67 @@ class EstateEngine:
             "n_tools": n_tools,
             "reach_dist": dist,
         }
+        if blast_depth > 1:
+            # multi-hop expansion of the unique packages, on the main stream
+            # after the join, fanned out to the findings through ``pos``
+            hops = self._blast_hops(
+                counts["uniq_pkgs"],
+                assembled["uniq_pkgs32"] if assembled is not None else None, blast_depth)
+            hop_depth = hops["hop_depth"][pos]
+            res["hop_depth"] = hop_depth
+            res["transitive_agents"] = hops["t_agents"][pos]
+            res["transitive_creds"] = hops["t_creds"][pos]
+            # one fp32 multiply, unrounded: rounding belongs to presentation
+            res["transitive_scores"] = torch.where(
+                hop_depth > 1, scores * self._hop_factor[hop_depth.to(torch.int64)],
+                torch.zeros_like(scores))
+        return res
+
+    def _blast_hops(self, uniq_pkgs, uniq_pkgs32, max_depth: int) -> dict:
+        """The multi-hop expansion of ``uniq_pkgs`` (node ids, int64): the
+        kernels of ops/csrc/blast_hops.hip on the GPU, ``cpu_ref.blast_hops``
+        on the CPU.  ``max_depth`` is clamped to [1, 5]."""
+        torch = self.torch
+        if self.use_gpu:
+            from agentbom_amd.ops import native
+
+            if uniq_pkgs32 is None:
+                uniq_pkgs32 = uniq_pkgs.to(torch.int32).contiguous()
+            out = native.blast_hops(uniq_pkgs32, self.rev, self.reach_index, self.agent_index,
+                                    ET_CONTAINS, max_depth, self._hops_ws)
+        else:
+            from agentbom_amd.ops import cpu_ref
+
+            hop_agents, t_creds, hop_depth = cpu_ref.blast_hops(
+                uniq_pkgs.numpy(), self.rev["row_off"].numpy(), self.rev["col"].numpy(),
+                self.rev["etype"].numpy(), ET_CONTAINS, ET_USES, ET_HAS_CRED,
+                self.fwd["row_off"].numpy(), self.fwd["col"].numpy(),
+                self.fwd["etype"].numpy(), max_depth)
+            out = {"hop_agents": torch.from_numpy(hop_agents),
+                   "t_creds": torch.from_numpy(t_creds),
+                   "hop_depth": torch.from_numpy(hop_depth)}
+        out["t_agents"] = out["hop_agents"].sum(dim=1, dtype=torch.int32)
+        out["uniq_pkgs"] = uniq_pkgs
+        return out
+
+    def transitive_blast(self, step_res=None, max_depth: int = 3) -> dict:
+        """Multi-hop delegation blast radius per unique matched package: who
+        is exposed transitively through agents that share servers.
+
+        Returns tensors on the engine's device, indexed by position in
+        ``uniq_pkgs`` (ascending package node ids of ``step_res``):
+        ``hop_agents`` int32 [U,4] (agents first reached at hop 2..5),
+        ``t_agents`` int32 [U] (their sum), ``t_creds`` int32 [U] (distinct
+        credentials on the servers of those agents) and ``hop_depth`` uint8
+        [U] (deepest hop that reached a new agent, else 1).  Semantics:
+        ``models.blast.expand_blast_radius_hops``; ``max_depth`` is clamped
+        to [1, 5]."""
+        torch = self.torch
+        if step_res is None:
+            step_res = self.step()
+        pkg_nodes = (step_res["pkg_idx"] + self.estate.pkg_base).to(torch.int64)
+        # pkg_idx arrives sorted: no re-sort needed
+        return self._blast_hops(torch.unique_consecutive(pkg_nodes), None, max_depth)
 
     def _score_cpu(self, counts, pos, pkg_nodes, win_idx, dist):
         """CPU oracle of the fused score_gather kernel: (scores, n_agents,

@@ -209,8 +209,11 @@ def expand_blast_radius_hops(
 ) -> None:
     """Multi-hop delegation BFS over agent<->server sharing, hop-decayed risk.
 
-    CPU reference semantics; at estate scale the same expansion runs as the
-    hop-limited GPU BFS with per-hop decay (ops/csrc/bfs.hip).
+    CPU reference semantics; at estate scale the same expansion runs per
+    matched package as the hop-limited level walk of ops/csrc/blast_hops.hip
+    (``EstateEngine.transitive_blast`` / ``step(blast_depth=k)``), which
+    returns the agents per hop, the deepest hop and the transitive credential
+    count, and applies the same decay table unrounded.
     """
     max_depth = max(1, min(max_depth, 5))
     if max_depth <= 1:

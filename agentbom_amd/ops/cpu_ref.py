@@ -398,3 +398,76 @@ def component_stats(comp, kind, num_components: int, num_kinds: int,
     if worst is not None:
         np.minimum.at(worst_min, comp, np.asarray(worst, dtype=np.uint32))
     return kind_counts, weight_sum, worst_min.view(np.int32)
+
+
+# ── multi-hop delegation expansion (oracle for csrc/blast_hops.hip) ─────────
+
+BLAST_HOPS_MAX_DEPTH = 5
+
+
+def blast_hops(pkgs, rev_off, rev_col, rev_et, et_contains, et_uses, et_has_cred,
+               fwd_off, fwd_col, fwd_et, max_depth: int):
+    """Multi-hop delegation blast radius per package node, as plain sets.
+
+    With srv(a) the distinct USES targets of agent a, ag(s) the distinct USES
+    sources of server s, cr(s) the distinct HAS_CRED targets of s and
+    D = clamp(max_depth, 1, 5): S0 = holders of p (reverse CONTAINS),
+    A_1 = ag(S0), F_1 = srv(A_1) \\ S0, then for h = 1..D-1
+    A_{h+1} = ag(F_h) \\ visited agents and, while h+1 < D,
+    F_{h+1} = srv(A_{h+1}) \\ visited servers; the walk stops at an empty
+    level.  The level BFS of models/blast.py expand_blast_radius_hops.
+
+    Returns ``(hop_agents int32 [U,4], t_creds int32 [U], hop_depth uint8
+    [U])``: |A_h| for h = 2..5, the distinct credentials on every server of
+    every transitive agent (h >= 2), and the largest h with |A_h| > 0, else 1.
+    """
+    depth = max(1, min(int(max_depth), BLAST_HOPS_MAX_DEPTH))
+    pkgs = np.asarray(pkgs, dtype=np.int64)
+    U = len(pkgs)
+    hop_agents = np.zeros((U, 4), dtype=np.int32)
+    t_creds = np.zeros(U, dtype=np.int32)
+    hop_depth = np.ones(U, dtype=np.uint8)
+
+    def neighbours(off, col, et, want):
+        cache: dict = {}
+
+        def of(node):
+            got = cache.get(node)
+            if got is None:
+                beg, end = int(off[node]), int(off[node + 1])
+                got = cache[node] = frozenset(
+                    int(col[e]) for e in range(beg, end) if et[e] == want)
+            return got
+        return of
+
+    holders = neighbours(rev_off, rev_col, rev_et, et_contains)
+    ag = neighbours(rev_off, rev_col, rev_et, et_uses)
+    srv = neighbours(fwd_off, fwd_col, fwd_et, et_uses)
+    cr = neighbours(fwd_off, fwd_col, fwd_et, et_has_cred)
+
+    def union(fn, nodes):
+        out: set = set()
+        for v in nodes:
+            out |= fn(v)
+        return out
+
+    for i, p in enumerate(pkgs):
+        s0 = set(holders(int(p)))
+        a1 = union(ag, s0)
+        seen_s, seen_a = set(s0), set(a1)
+        frontier = union(srv, a1) - s0
+        seen_s |= frontier
+        transitive: set = set()
+        for h in range(1, depth):
+            level = union(ag, frontier) - seen_a
+            if not level:
+                break
+            seen_a |= level
+            transitive |= level
+            hop_agents[i, h - 1] = len(level)
+            hop_depth[i] = h + 1
+            if h + 1 < depth:
+                frontier = union(srv, level) - seen_s
+                seen_s |= frontier
+        t_creds[i] = len(union(cr, union(srv, transitive)))
+    return hop_agents, t_creds, hop_depth

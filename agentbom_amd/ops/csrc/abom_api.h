@@ -130,6 +130,30 @@ int abom_blast_counts_indexed_sized(
     void* queue, void* counters, void* host_counters,
     void* out_counts, void* out_overflow, void* stream);
 
+// blast_hops.hip (multi-hop delegation expansion per package from the reach
+// index and the agent index: out_hop_agents int32 [n,4] = |A_h| for h = 2..5,
+// out_creds int32 [n], out_depth u8 [n], out_overflow u8 [n]; counters is
+// {queued packages, overflowed rows}; max_depth is clamped to [1, 5].
+// abom_blast_hops_cap returns a cap of the wave kernel, not a hipError_t:
+// 0 = visited servers, 1 = visited agents, 2 = credentials, else -1)
+int abom_blast_hops_cap(int which);
+int abom_blast_hops(
+    const void* pkgs, long long n,
+    const void* rev_off, const void* rev_col, const void* rev_et, int et_contains,
+    const void* reach_off, const void* reach_col, long long row_base, long long num_rows,
+    const void* agent_off, const void* agent_srv, long long num_agents, int max_depth,
+    void* queue, void* counters,
+    void* out_hop_agents, void* out_creds, void* out_depth, void* out_overflow, void* stream);
+// the same over at most n_cap packages: the count is the device long long
+// n_dev; the counters are also copied to host_counters (pinned u32[2])
+int abom_blast_hops_sized(
+    const void* pkgs, const void* n_dev, long long n_cap,
+    const void* rev_off, const void* rev_col, const void* rev_et, int et_contains,
+    const void* reach_off, const void* reach_col, long long row_base, long long num_rows,
+    const void* agent_off, const void* agent_srv, long long num_agents, int max_depth,
+    void* queue, void* counters, void* host_counters,
+    void* out_hop_agents, void* out_creds, void* out_depth, void* out_overflow, void* stream);
+
 // paths.hip (edge_weight and node_gate are nullable)
 int abom_path_relax(
     const void* edge_src, const void* col, const void* etype, const void* edge_weight,

@@ -136,6 +136,23 @@ _SIGNATURES = {
         _c, _c, _c,        # queue, counters, host_counters
         _c, _c, _c,        # out_counts, out_overflow, stream
     ], _i32),
+    "abom_blast_hops_cap": ([_i32], _i32),  # which
+    "abom_blast_hops": ([
+        _c, _i64,              # pkgs, n
+        _c, _c, _c, _i32,      # rev_off, rev_col, rev_et, et_contains
+        _c, _c, _i64, _i64,    # reach_off, reach_col, row_base, num_rows
+        _c, _c, _i64, _i32,    # agent_off, agent_srv, num_agents, max_depth
+        _c, _c,                # queue, counters
+        _c, _c, _c, _c, _c,    # out_hop_agents, out_creds, out_depth, out_overflow, stream
+    ], _i32),
+    "abom_blast_hops_sized": ([
+        _c, _c, _i64,          # pkgs, n_dev, n_cap
+        _c, _c, _c, _i32,      # rev_off, rev_col, rev_et, et_contains
+        _c, _c, _i64, _i64,    # reach_off, reach_col, row_base, num_rows
+        _c, _c, _i64, _i32,    # agent_off, agent_srv, num_agents, max_depth
+        _c, _c, _c,            # queue, counters, host_counters
+        _c, _c, _c, _c, _c,    # out_hop_agents, out_creds, out_depth, out_overflow, stream
+    ], _i32),
     "abom_path_relax": ([
         _c, _c, _c, _c,  # edge_src, col, etype, edge_weight
         _c, _c, _c, _c,  # cur, nxt, node_boost, etype_boost
@@ -1010,6 +1027,235 @@ def blast_counts_indexed_sized(pkgs, n_dev, rev, index: dict, et_contains: int,
     done.synchronize()
     queued, n_overflow = host.tolist()
     return out_counts, out_overflow, queued, n_overflow
+
+
+# ── Multi-hop delegation expansion (ops/csrc/blast_hops.hip) ───────────────
+
+# LDS caps of blast_hops_wave_kernel (HOPS_*_CAP, csrc/blast_hops.hip): a
+# package whose visited servers, visited agents or credential union pass one
+# is resolved by the exact join.  ``abom_blast_hops_cap`` reports the values
+# the library was built with.
+BLAST_HOPS_SRV_CAP = 448
+BLAST_HOPS_AG_CAP = 192
+BLAST_HOPS_CR_CAP = 448
+BLAST_HOPS_MAX_DEPTH = 5
+
+
+def _hops_inputs(pkgs32, rev: dict, index: dict, agent_index: dict):
+    """Argument checks shared by the blast_hops bindings; returns the device."""
+    import torch
+
+    dev = pkgs32.device
+    if dev.type != "cuda":
+        raise ValueError(f"blast_hops: pkgs32 on {dev}, expected a GPU tensor")
+    _require(pkgs32, "pkgs32", torch.int32, dev)
+    _require(rev["row_off"], "rev.row_off", torch.int64, dev)
+    E = rev["col"].numel()
+    _require(rev["col"], "rev.col", torch.int32, dev)
+    _require(rev["etype"], "rev.etype", torch.uint8, dev, E)
+    _require(index["reach_off"], "index.reach_off", torch.int32, dev)
+    if index["reach_off"].dim() != 2 or index["reach_off"].shape[1] != 4:
+        raise ValueError("blast_hops: index.reach_off is not [rows, 4]")
+    _require(index["reach_col"], "index.reach_col", torch.int32, dev)
+    _require(agent_index["agent_off"], "agent_index.agent_off", torch.int32, dev)
+    if agent_index["agent_off"].numel() < 1:
+        raise ValueError("blast_hops: agent_index.agent_off is empty")
+    _require(agent_index["agent_srv"], "agent_index.agent_srv", torch.int32, dev)
+    return dev
+
+
+def _hops_expand(torch, beg, cnt, carry, col):
+    """Segment gather: ``col[beg[i]:beg[i]+cnt[i]]`` for every i, each entry
+    paired with ``carry[i]``."""
+    dev = beg.device
+    total = int(cnt.sum().item())
+    if total == 0:
+        e = torch.empty(0, dtype=torch.int64, device=dev)
+        return e, e.clone()
+    rep = torch.repeat_interleave(torch.arange(beg.numel(), device=dev), cnt)
+    ends = torch.cumsum(cnt, 0)
+    within = torch.arange(total, device=dev) - (ends - cnt)[rep]
+    return col[beg[rep] + within].to(torch.int64), carry[rep]
+
+
+def _blast_hops_join(pkgs, rev: dict, index: dict, agent_index: dict, et_contains: int,
+                     depth: int):
+    """The expansion of :func:`blast_hops` as sort-based set operations on
+    (package position << 32 | node) keys: exact for any set size, the path of
+    the rows that overflowed an LDS cap.  ``pkgs`` int64 [k]; returns
+    (hop_agents int32 [k,4], t_creds int32 [k], hop_depth uint8 [k])."""
+    import torch
+
+    dev = pkgs.device
+    k = pkgs.numel()
+    reach_off = index["reach_off"].to(torch.int64)
+    reach_col = index["reach_col"]
+    row_base, S = int(index["row_base"]), reach_off.shape[0]
+    agent_off = agent_index["agent_off"].to(torch.int64)
+    agent_srv = agent_index["agent_srv"]
+    A = agent_off.numel() - 1
+
+    def split(keys):
+        return keys >> 32, keys & 0xFFFFFFFF
+
+    def server_segment(keys, first):
+        # segment ``first`` (0 agents, 1 creds) of the servers' index rows;
+        # a server without a row has no neighbours, as in the kernel
+        pos, node = split(keys)
+        row = node - row_base
+        ok = (row >= 0) & (row < S)
+        row = row.clamp(0, max(S - 1, 0))
+        if S == 0:
+            return keys[:0]
+        beg = reach_off[row, first]
+        cnt = torch.where(ok, reach_off[row, first + 1] - beg, torch.zeros_like(beg))
+        nbr, carry = _hops_expand(torch, beg, cnt, pos, reach_col)
+        return torch.unique((carry << 32) | nbr)
+
+    def servers_of(keys):
+        pos, node = split(keys)
+        ok = node < A
+        if A == 0:
+            return keys[:0]
+        a = node.clamp(0, A - 1)
+        beg = agent_off[a]
+        cnt = torch.where(ok, agent_off[a + 1] - beg, torch.zeros_like(beg))
+        nbr, carry = _hops_expand(torch, beg, cnt, pos, agent_srv)
+        return torch.unique((carry << 32) | nbr)
+
+    def minus(keys, seen):
+        return keys[~torch.isin(keys, seen)]
+
+    def per_pos(keys):
+        return torch.bincount(keys >> 32, minlength=k).to(torch.int32)
+
+    pos = torch.arange(k, device=dev)
+    row_off = rev["row_off"]
+    beg = row_off[pkgs]
+    e_col, e_pos = _hops_expand(torch, beg, row_off[pkgs + 1] - beg, pos,
+                                torch.arange(rev["col"].numel(), device=dev))
+    held = rev["etype"][e_col] == et_contains
+    s0 = torch.unique((e_pos[held] << 32) | rev["col"][e_col[held]].to(torch.int64))
+    a1 = server_segment(s0, 0)
+    seen_s, seen_a = s0, a1
+    frontier = minus(servers_of(a1), seen_s)
+    seen_s = torch.cat([seen_s, frontier])
+    hop_agents = torch.zeros(k, 4, dtype=torch.int32, device=dev)
+    levels = []
+    for h in range(1, depth):
+        level = minus(server_segment(frontier, 0), seen_a)
+        if level.numel() == 0:
+            break
+        seen_a = torch.cat([seen_a, level])
+        levels.append(level)
+        hop_agents[:, h - 1] = per_pos(level)
+        if h + 1 < depth:
+            frontier = minus(servers_of(level), seen_s)
+            seen_s = torch.cat([seen_s, frontier])
+    t_creds = torch.zeros(k, dtype=torch.int32, device=dev)
+    if levels:
+        t_creds = per_pos(server_segment(servers_of(torch.cat(levels)), 1))
+    # a level is empty for a package once one before it was
+    hop_depth = (1 + (hop_agents > 0).sum(dim=1)).to(torch.uint8)
+    return hop_agents, t_creds, hop_depth
+
+
+def blast_hops(pkgs32, rev: dict, index: dict, agent_index: dict, et_contains: int,
+               max_depth: int, workspace: Optional[dict] = None) -> dict:
+    """Multi-hop delegation blast radius of package nodes (csrc/blast_hops.hip;
+    semantics: ``cpu_ref.blast_hops``).  ``index`` is the per-server reach
+    index, ``agent_index`` the per-agent server index
+    (``graph.gpu_engine.build_reach_index`` / ``build_agent_index``);
+    ``max_depth`` is clamped to [1, 5].
+
+    Returns device tensors ``hop_agents`` int32 [n,4] (agents first reached
+    at hop 2..5), ``t_creds`` int32 [n] and ``hop_depth`` uint8 [n].  A
+    thread-per-package pass finishes the packages whose direct agents use no
+    server outside the holders; a wave-per-package pass walks the rest in LDS;
+    rows that pass a cap (BLAST_HOPS_*_CAP) are recomputed by the exact join.
+    The one host read is {queued, overflowed}, left as ints in
+    ``workspace["hops_queued"]`` and ``workspace["hops_overflow"]``.  Depth 1
+    and an empty package list launch nothing."""
+    import torch
+
+    dev = _hops_inputs(pkgs32, rev, index, agent_index)
+    ws = workspace if workspace is not None else {}
+    depth = max(1, min(int(max_depth), BLAST_HOPS_MAX_DEPTH))
+    n = pkgs32.numel()
+    ws["hops_queued"] = ws["hops_overflow"] = 0
+    if n == 0 or depth == 1:
+        return {"hop_agents": torch.zeros(n, 4, dtype=torch.int32, device=dev),
+                "t_creds": torch.zeros(n, dtype=torch.int32, device=dev),
+                "hop_depth": torch.ones(n, dtype=torch.uint8, device=dev)}
+    lib = load()
+    hop_agents = torch.empty(n, 4, dtype=torch.int32, device=dev)
+    t_creds = torch.empty(n, dtype=torch.int32, device=dev)
+    hop_depth = torch.empty(n, dtype=torch.uint8, device=dev)
+    overflow = torch.empty(n, dtype=torch.uint8, device=dev)
+    queue = _buf(ws, "hops_queue", n, torch.int32, dev)
+    counters = _buf(ws, "hops_counters", 2, torch.int32, dev)
+    rc = lib.abom_blast_hops(
+        _ptr(pkgs32), n,
+        _ptr(rev["row_off"]), _ptr(rev["col"]), _ptr(rev["etype"]), int(et_contains),
+        _ptr(index["reach_off"]), _ptr(index["reach_col"]),
+        int(index["row_base"]), index["reach_off"].shape[0],
+        _ptr(agent_index["agent_off"]), _ptr(agent_index["agent_srv"]),
+        agent_index["agent_off"].numel() - 1, depth,
+        _ptr(queue), _ptr(counters),
+        _ptr(hop_agents), _ptr(t_creds), _ptr(hop_depth), _ptr(overflow), _stream(),
+    )
+    _check(rc, "abom_blast_hops")
+    ws["hops_queued"], ws["hops_overflow"] = counters.tolist()
+    if ws["hops_overflow"]:
+        ov = torch.nonzero(overflow).flatten()
+        heavy = _blast_hops_join(pkgs32[ov].to(torch.int64), rev, index, agent_index,
+                                 int(et_contains), depth)
+        hop_agents[ov], t_creds[ov], hop_depth[ov] = heavy
+    return {"hop_agents": hop_agents, "t_creds": t_creds, "hop_depth": hop_depth}
+
+
+def blast_hops_sized(pkgs32, n_dev, rev: dict, index: dict, agent_index: dict,
+                     et_contains: int, max_depth: int, workspace: dict):
+    """The two passes of :func:`blast_hops` for a package count that is on the
+    device: ``pkgs32`` is a buffer of some capacity, ``n_dev`` an int64 tensor
+    whose first element says how many of its entries count, so the call can
+    be enqueued behind the kernel that writes them with no host read.  Rows
+    from ``n_dev`` on are not written, and overflowed rows are left flagged:
+    returns (hop_agents [capacity,4], t_creds, hop_depth, overflow u8
+    [capacity], queued, overflowed rows), the last two through pinned host
+    memory after a wait for the stream."""
+    import torch
+
+    dev = _hops_inputs(pkgs32, rev, index, agent_index)
+    _require(n_dev, "n_dev", torch.int64, dev)
+    lib = load()
+    n_cap = pkgs32.numel()
+    hop_agents = torch.empty(n_cap, 4, dtype=torch.int32, device=dev)
+    t_creds = torch.empty(n_cap, dtype=torch.int32, device=dev)
+    hop_depth = torch.empty(n_cap, dtype=torch.uint8, device=dev)
+    overflow = torch.empty(n_cap, dtype=torch.uint8, device=dev)
+    queue = _buf(workspace, "hops_queue", n_cap, torch.int32, dev)
+    counters = _buf(workspace, "hops_counters", 2, torch.int32, dev)
+    host = workspace.get("hops_host_counters")
+    if host is None:
+        host = workspace["hops_host_counters"] = torch.zeros(
+            2, dtype=torch.int32, pin_memory=True)
+    rc = lib.abom_blast_hops_sized(
+        _ptr(pkgs32), _ptr(n_dev), n_cap,
+        _ptr(rev["row_off"]), _ptr(rev["col"]), _ptr(rev["etype"]), int(et_contains),
+        _ptr(index["reach_off"]), _ptr(index["reach_col"]),
+        int(index["row_base"]), index["reach_off"].shape[0],
+        _ptr(agent_index["agent_off"]), _ptr(agent_index["agent_srv"]),
+        agent_index["agent_off"].numel() - 1, int(max_depth),
+        _ptr(queue), _ptr(counters), _ptr(host),
+        _ptr(hop_agents), _ptr(t_creds), _ptr(hop_depth), _ptr(overflow), _stream(),
+    )
+    _check(rc, "abom_blast_hops_sized")
+    done = torch.cuda.Event()
+    done.record()
+    done.synchronize()
+    queued, n_overflow = host.tolist()
+    return hop_agents, t_creds, hop_depth, overflow, queued, n_overflow
 
 
 def risk_weights_array() -> np.ndarray:

@@ -47,7 +47,11 @@ from agentbom_amd.scan.synth import (
 
 
 class DistEstateEngine:
-    """One rank's engine over its hash partition of the global estate."""
+    """One rank's engine over its hash partition of the global estate.
+
+    The multi-hop delegation expansion (``EstateEngine.transitive_blast``,
+    ``step(blast_depth > 1)``) is not distributed: this engine's step has no
+    ``blast_depth`` and returns no hop keys."""
 
     def __init__(self, estate: SyntheticEstate, rank: int, world: int,
                  device: str = "cuda", group=None):
