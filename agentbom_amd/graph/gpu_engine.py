@@ -17,6 +17,9 @@ construction) and stays resident in HBM3E.  On top of it:
                          instead); AGENT_BOM_MATCH_BY_WINDOW=0, or an estate
                          without a dedup layout, keeps the row kernel there
 - ``dependency_reach()`` multi-source BFS from all agents (ops/csrc/bfs.hip)
+- ``agent_reach()``      hop count per (target, agent) for a set of agents:
+                         bit-parallel multi-source BFS, 64 agents per 64-bit
+                         word (ops/csrc/reach_sets.hip)
 - ``blast_counts()``     segmented joins: per-finding distinct agent/cred/
                          tool reach with CWE-impact filtering.  On the GPU
                          the matched packages are joined against a
@@ -514,6 +517,7 @@ class EstateEngine:
 
         self.agent_ids = torch.arange(estate.n_agents, dtype=torch.int32, device=dev)
         self._bfs_ws: dict = {}
+        self._reach_ws: dict = {}  # ops/csrc/reach_sets.hip state, see agent_reach
         # out-degree sum of the BFS sources: a property of the CSR and the
         # agent ids, like pkg_win_range, so the reach BFS need not read it
         # back from the device every step
@@ -634,6 +638,57 @@ class EstateEngine:
             etype=self.fwd["etype"].numpy(), allowed_mask=mask,
         )
         return self.torch.from_numpy(dist.view(np.int32)).to(self.torch.int32)
+
+    def agent_reach(self, agent_ids, targets=None, max_depth: int = 16) -> dict:
+        """Which of ``agent_ids`` reach which ``targets``, and in how many hops.
+
+        ``agent_ids``: node ids of the source agents (any integer tensor or
+        sequence; duplicates keep their own column).  ``targets``: distinct
+        node ids, by default every package node of the estate; pass the
+        matched unique packages of a step (``unique(step["pkg_idx"]) +
+        estate.pkg_base``) to ask about those alone.  The walk is that of
+        :meth:`dependency_reach`: forward CSR, same edge types, and a node at
+        distance ``max_depth`` is recorded but not expanded.
+
+        Returns tensors on the engine's device: ``hops`` uint8 [T, S] (255 =
+        not reached within ``max_depth``), ``agents`` int32 [S], ``targets``
+        int32 [T], ``n_reaching`` int32 [T] (sources with ``hops != 255``) and
+        ``min_hop`` uint8 [T] (255 where none).  On a CUDA device the hops
+        come from ``native.reach_hops`` (ops/csrc/reach_sets.hip), on the CPU
+        from ``cpu_ref.reach_hops``."""
+        torch = self.torch
+        dev = self.device
+        mask = (1 << ET_USES) | (1 << ET_CONTAINS) | (1 << ET_HAS_CRED) | (1 << ET_PROVIDES_TOOL)
+        agents = torch.as_tensor(agent_ids, device=dev).to(torch.int32).reshape(-1).contiguous()
+        if targets is None:
+            targets = self.estate.pkg_base + torch.arange(
+                self.N - self.estate.pkg_base, dtype=torch.int32, device=dev)
+        targets = torch.as_tensor(targets, device=dev).to(torch.int32).reshape(-1).contiguous()
+        if self.use_gpu:
+            from agentbom_amd.ops import native
+
+            hops = native.reach_hops(
+                self.fwd["row_off"], self.fwd["col"], agents, targets, self.N,
+                etype=self.fwd["etype"], allowed_mask=mask, max_depth=max_depth,
+                workspace=self._reach_ws)
+        else:
+            from agentbom_amd.ops import cpu_ref
+
+            hops = torch.from_numpy(cpu_ref.reach_hops(
+                self.fwd["row_off"].numpy(), self.fwd["col"].numpy(), agents.numpy(),
+                targets.numpy(), self.N, etype=self.fwd["etype"].numpy(),
+                allowed_mask=mask, max_depth=max_depth))
+        if agents.numel():
+            min_hop = hops.min(dim=1).values
+        else:
+            min_hop = torch.full((targets.numel(),), 255, dtype=torch.uint8, device=dev)
+        return {
+            "hops": hops,
+            "agents": agents,
+            "targets": targets,
+            "n_reaching": (hops != 255).sum(dim=1, dtype=torch.int32),
+            "min_hop": min_hop,
+        }
 
     def _expand(self, csr, rows, carry, want_type: int):
         """Segmented gather: neighbors of ``rows`` with ``carry`` repeated.

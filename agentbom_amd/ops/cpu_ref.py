@@ -108,6 +108,41 @@ def bfs_level(row_off, col, frontier, dist, level: int,
     return np.asarray(nxt, dtype=np.int64)
 
 
+def reach_hops(row_off, col, sources, targets, num_nodes: int,
+               etype: Optional[np.ndarray] = None, allowed_mask: int = 0xFFFFFFFF,
+               max_depth: int = 16):
+    """Per-source reach, from the definition: one queue BFS per source.
+
+    Returns u8 ``hops[t, s]`` = distance from ``sources[s]`` to ``targets[t]``
+    when it is at most ``max_depth`` (clamped to [0, 254]), else 255.  A node
+    at distance ``max_depth`` is recorded but not expanded, as in
+    ``UnifiedGraph.bfs``; duplicate sources each keep their column."""
+    from collections import deque
+
+    sources = np.asarray(sources, dtype=np.int64)
+    targets = np.asarray(targets, dtype=np.int64)
+    depth = max(0, min(int(max_depth), 254))
+    hops = np.full((len(targets), len(sources)), 255, dtype=np.uint8)
+    for s, src in enumerate(sources):
+        dist = np.full(num_nodes, -1, dtype=np.int64)
+        dist[src] = 0
+        queue = deque([int(src)])
+        while queue:
+            u = queue.popleft()
+            if dist[u] >= depth:
+                continue
+            for e in range(int(row_off[u]), int(row_off[u + 1])):
+                if etype is not None and not ((allowed_mask >> int(etype[e])) & 1):
+                    continue
+                v = int(col[e])
+                if dist[v] < 0:
+                    dist[v] = dist[u] + 1
+                    queue.append(v)
+        d = dist[targets]
+        hops[d >= 0, s] = d[d >= 0]
+    return hops
+
+
 def impact_query(row_off, col, query_sources, etype=None, allowed_mask: int = 0xFFFFFFFF,
                  max_hops: int = 4, max_nodes: int = 4096):
     """Reference bounded blast-radius query.  Returns list of {node: hop}."""

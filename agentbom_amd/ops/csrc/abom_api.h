@@ -83,6 +83,22 @@ int abom_bfs_run_ex(
     const void* rev_off, const void* rev_col, const void* rev_et,
     int begun, long long sources_degree, void* host_counters, void* stream);
 
+// reach_sets.hip (one pass of per-source reach for n_sources <= 64 * words
+// sources, words in 1..4: hops u8 [T, hops_stride] gets the hop count of
+// source j at column col_base + j of every target row it reaches within
+// max_depth, clamped to [0, 254], and is otherwise left as the caller filled
+// it; seen, cur and nxt are u64 [num_nodes * words], cur and nxt all-zero on
+// entry and on return; the three queues are u32 [num_nodes * words];
+// counters is device u32 [2]; host_counters is pinned host u32 [2], nullable.
+// Returns the number of levels run or a negated hipError_t)
+int abom_reach_hops(
+    const void* row_off, const void* col, const void* etype, unsigned int allowed_mask,
+    const void* sources, int n_sources, int words, long long num_nodes,
+    const void* target_slot, void* hops, long long hops_stride, long long col_base,
+    int max_depth,
+    void* seen, void* cur, void* nxt, void* queue_a, void* queue_b, void* heavy_queue,
+    void* counters, void* host_counters, void* stream);
+
 // query.hip
 int abom_impact_query(
     const void* row_off, const void* col, const void* etype, unsigned int allowed_mask,

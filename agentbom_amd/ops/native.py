@@ -93,6 +93,14 @@ _SIGNATURES = {
         _c, _c, _c,           # rev_off, rev_col, rev_et
         _i32, _i64, _c, _c,   # begun, sources_degree, host_counters, stream
     ], _i32),
+    "abom_reach_hops": ([
+        _c, _c, _c, _u32,        # row_off, col, etype, allowed_mask
+        _c, _i32, _i32, _i64,    # sources, n_sources, words, num_nodes
+        _c, _c, _i64, _i64,      # target_slot, hops, hops_stride, col_base
+        _i32,                    # max_depth
+        _c, _c, _c, _c, _c, _c,  # seen, cur, nxt, queue_a, queue_b, heavy_queue
+        _c, _c, _c,              # counters, host_counters, stream
+    ], _i32),
     "abom_impact_query": ([
         _c, _c, _c, _u32,      # row_off, col, etype, allowed_mask
         _c, _i32, _i32, _i32,  # query_sources, num_queries, max_hops, max_nodes_per_query
@@ -901,6 +909,119 @@ def bfs_level_edges(row_off, col, edge_src, frontier_dist_level: int, dist,
     _check(rc, "abom_bfs_expand_edges")
     n = int(ctr[0].item())
     return nxt[:n].clone()
+
+
+# Sources per 64-bit word and words per node of a reach pass (csrc/reach_sets.hip)
+REACH_WORD_SOURCES = 64
+REACH_MAX_WORDS = 4
+REACH_UNREACHED = 255
+
+
+def reach_hops_chunks(row_off, col, sources, targets, num_nodes: int, etype=None,
+                      allowed_mask: int = 0xFFFFFFFF, max_depth: int = 16,
+                      workspace: Optional[dict] = None, chunk_sources: Optional[int] = None):
+    """Per-source reach in pieces: a generator of ``(first, hops)`` where
+    ``hops`` is the u8 ``[T, n]`` device tensor of sources ``first .. first+n``
+    (``n <= chunk_sources``; one piece of all S sources when it is None).  A
+    caller that cannot hold ``T * S`` bytes consumes one piece at a time; see
+    :func:`reach_hops` for the contract of a piece.
+
+    A piece is walked in passes of up to 64 * W sources, W = the fewest 64-bit
+    words per node that hold the pass, at most 4: the sources of a pass share
+    one bit-parallel BFS.  ``workspace`` keeps the state buffers between calls
+    and is left with ``levels`` (the deepest pass) and ``passes`` as ints.
+    """
+    import torch
+
+    dev = row_off.device
+    if dev.type != "cuda":
+        raise ValueError("reach_hops: the graph must be on a cuda device")
+    _require(sources, "sources", torch.int32, dev)
+    _require(targets, "targets", torch.int32, dev)
+    S, T = sources.numel(), targets.numel()
+    ws = workspace if workspace is not None else {}
+    ws["levels"], ws["passes"] = 0, 0
+    if S == 0:
+        yield 0, torch.empty((T, 0), dtype=torch.uint8, device=dev)
+        return
+    chunk = S if chunk_sources is None else int(chunk_sources)
+    if chunk < 1:
+        raise ValueError("reach_hops: chunk_sources must be positive")
+    if T == 0:
+        for first in range(0, S, chunk):
+            yield first, torch.empty((0, min(chunk, S - first)), dtype=torch.uint8, device=dev)
+        return
+    lib = load()
+    per_word = REACH_WORD_SOURCES
+    max_words = min(REACH_MAX_WORDS, (min(chunk, S) + per_word - 1) // per_word)
+    if num_nodes * max_words >= 1 << 32:
+        raise ValueError(f"reach_hops: {num_nodes} nodes x {max_words} words exceeds the "
+                         "u32 frontier entries; use fewer sources per chunk")
+    cells = num_nodes * max_words
+    seen = _buf(ws, "reach_seen", cells, torch.int64, dev)
+    cur = _buf(ws, "reach_cur", cells, torch.int64, dev, zero=True)
+    nxt = _buf(ws, "reach_nxt", cells, torch.int64, dev, zero=True)
+    qa = _buf(ws, "reach_queue_a", cells, torch.int32, dev)
+    qb = _buf(ws, "reach_queue_b", cells, torch.int32, dev)
+    hq = _buf(ws, "reach_heavy", cells, torch.int32, dev)
+    ctr = _buf(ws, "reach_counters", 2, torch.int32, dev, zero=True)
+    host_ctr = ws.get("reach_host_counters")
+    if host_ctr is None:
+        # pinned, so the per-level count read is a direct copy
+        host_ctr = ws["reach_host_counters"] = torch.zeros(2, dtype=torch.int32, pin_memory=True)
+    if ws.get("reach_dirty"):
+        # a pass that did not finish may have left bits behind
+        cur.zero_()
+        nxt.zero_()
+    slot = _buf(ws, "reach_target_slot", num_nodes, torch.int32, dev)[:num_nodes]
+    slot.fill_(-1)
+    slot[targets.to(torch.int64)] = torch.arange(T, dtype=torch.int32, device=dev)
+    sources = sources.contiguous()
+    et = _ptr(etype) if etype is not None else None
+    for first in range(0, S, chunk):
+        n = min(chunk, S - first)
+        hops = torch.full((T, n), REACH_UNREACHED, dtype=torch.uint8, device=dev)
+        done = 0
+        while done < n:
+            words = min(REACH_MAX_WORDS, (n - done + per_word - 1) // per_word)
+            count = min(n - done, words * per_word)
+            ws["reach_dirty"] = True
+            rc = lib.abom_reach_hops(
+                _ptr(row_off), _ptr(col), et, allowed_mask,
+                ctypes.c_void_p(sources.data_ptr() + 4 * (first + done)), count, words,
+                num_nodes, _ptr(slot), _ptr(hops), n, done, max_depth,
+                _ptr(seen), _ptr(cur), _ptr(nxt), _ptr(qa), _ptr(qb), _ptr(hq),
+                _ptr(ctr), _ptr(host_ctr), _stream(),
+            )
+            if rc < 0:
+                _check(-rc, "abom_reach_hops")
+            ws["reach_dirty"] = False
+            ws["levels"] = max(ws["levels"], rc)
+            ws["passes"] += 1
+            done += count
+        yield first, hops
+
+
+def reach_hops(row_off, col, sources, targets, num_nodes: int, etype=None,
+               allowed_mask: int = 0xFFFFFFFF, max_depth: int = 16,
+               workspace: Optional[dict] = None):
+    """Per-source reach: u8 ``hops[t, s]`` = BFS distance from ``sources[s]``
+    to ``targets[t]`` over the CSR (``row_off`` int64, ``col`` int32, edges
+    filtered by ``etype``/``allowed_mask``) when it is at most ``max_depth``
+    (clamped to [0, 254]), else 255.  ``sources`` and ``targets`` are int32
+    node ids in [0, num_nodes) on the graph's device; duplicate sources each
+    keep their column, targets are distinct.  ``max_depth`` is that of
+    ``UnifiedGraph.bfs``: a node at that distance is recorded, not expanded.
+    S == 0 or T == 0 returns an empty tensor without a launch.
+
+    The whole ``[T, S]`` matrix is one tensor here; :func:`reach_hops_chunks`
+    yields it in column pieces when it would be too large.  ``workspace``:
+    see there (``levels`` and ``passes`` are left as ints).
+    """
+    for _first, hops in reach_hops_chunks(row_off, col, sources, targets, num_nodes,
+                                          etype=etype, allowed_mask=allowed_mask,
+                                          max_depth=max_depth, workspace=workspace):
+        return hops
 
 
 def impact_query(row_off, col, query_sources, etype=None, allowed_mask: int = 0xFFFFFFFF,
