@@ -37,7 +37,7 @@
 // does not know it).
 
 #include "abom_api.h"
-#include "abom_common.h"
+#include "abom_wave.h"
 
 namespace abom {
 
@@ -50,12 +50,6 @@ enum { CTR_NEXT = 0, CTR_HEAVY = 1, CTR_DEGREE = 2, CTR_OPEN = 3, CTR_SLOTS = 4 
 // Entries of the per-block LDS claim queue of bfs_expand_kernel and
 // bfs_expand_heavy_kernel (16 KiB).
 constexpr unsigned BFS_STAGE = 4096;
-
-// One atomic per wave: lanes accumulate locally, reduce, lane 0 adds.
-__device__ __forceinline__ void wave_add_degree(unsigned int* dst, unsigned v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, v);
-}
 
 // Claim v for `level` and append it to the next frontier.  Returns v's
 // out-degree when this thread won the claim, 0 otherwise.  The relaxed
@@ -72,52 +66,18 @@ __device__ __forceinline__ unsigned claim_and_append(
     return (unsigned)(row_off[v + 1] - row_off[v]);
 }
 
-// Per-block LDS claim queue of the two vertex-frontier kernels.  `n` counts
-// the claims since the last flush and may pass BFS_STAGE: the claims past it
-// went straight to next_frontier.
-struct ClaimStage {
-    uint32_t v[BFS_STAGE];
-    unsigned n;
-    unsigned base;  // the block's first slot of next_frontier, set by the flush
-};
-
-// claim_and_append with the append staged: the slot comes from an LDS atomic,
-// and only a claim that finds the queue full pays the global one.
+// claim_and_append with the append staged (stage_push): only a claim that
+// finds the LDS queue full pays the global atomic.
 __device__ __forceinline__ unsigned claim_and_stage(
     uint32_t v, uint32_t level, uint32_t* __restrict__ dist,
-    const uint64_t* __restrict__ row_off, ClaimStage& st,
+    const uint64_t* __restrict__ row_off, BlockStage<BFS_STAGE>& st,
     uint32_t* __restrict__ next_frontier, unsigned int* __restrict__ next_count,
     long long capacity) {
     if (dist[v] != ABOM_UNVISITED ||
         atomicCAS(&dist[v], ABOM_UNVISITED, level) != ABOM_UNVISITED)
         return 0;
-    const unsigned slot = atomicAdd(&st.n, 1u);
-    if (slot < BFS_STAGE) {
-        st.v[slot] = v;
-    } else {
-        const unsigned idx = atomicAdd(next_count, 1u);
-        if ((long long)idx < capacity) next_frontier[idx] = v;
-    }
+    stage_push(v, st, next_frontier, next_count, capacity);
     return (unsigned)(row_off[v + 1] - row_off[v]);
-}
-
-// Whole block: reserve the queue's slots of next_frontier with ONE atomic and
-// copy it out coalesced.  Barriers inside; the caller empties the queue
-// (st.n = 0, then a barrier) before the next claim.
-__device__ __forceinline__ void stage_flush(
-    ClaimStage& st, uint32_t* __restrict__ next_frontier,
-    unsigned int* __restrict__ next_count, long long capacity) {
-    __syncthreads();
-    const unsigned n = st.n < BFS_STAGE ? st.n : BFS_STAGE;
-    if (threadIdx.x == 0 && n) st.base = atomicAdd(next_count, n);
-    __syncthreads();
-    if (n) {
-        const unsigned base = st.base;
-        for (unsigned k = threadIdx.x; k < n; k += blockDim.x) {
-            const unsigned idx = base + k;
-            if ((long long)idx < capacity) next_frontier[idx] = st.v[k];
-        }
-    }
 }
 
 // Pass over the frontier: expand vertices with degree < WAVE_DEG inline;
@@ -140,7 +100,7 @@ __global__ __launch_bounds__(256) void bfs_expand_kernel(
     unsigned int* __restrict__ next_degree_sum,
     long long capacity) {
     constexpr uint64_t WAVE_DEG = 64;
-    __shared__ ClaimStage st;
+    __shared__ BlockStage<BFS_STAGE> st;
     __shared__ unsigned block_deg;
     const long long stride = (long long)gridDim.x * blockDim.x;
     const long long rounds = (frontier_size + stride - 1) / stride;
@@ -167,7 +127,7 @@ __global__ __launch_bounds__(256) void bfs_expand_kernel(
         stage_flush(st, next_frontier, next_count, capacity);
     }
     // degree sum: wave reduce, one LDS atomic per wave, one global per block
-    for (int off = 32; off > 0; off >>= 1) my_deg += __shfl_down(my_deg, off, 64);
+    my_deg = wave_sum(my_deg);
     __syncthreads();
     if ((threadIdx.x & 63) == 0 && my_deg) atomicAdd(&block_deg, my_deg);
     __syncthreads();
@@ -190,28 +150,26 @@ __global__ __launch_bounds__(256) void bfs_expand_heavy_kernel(
     unsigned int* __restrict__ next_count,
     unsigned int* __restrict__ next_degree_sum,
     long long capacity) {
-    __shared__ ClaimStage st;
+    __shared__ BlockStage<BFS_STAGE> st;
     const unsigned heavy_size = *heavy_size_ptr;
-    const int lane = threadIdx.x & 63;
-    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
     // the block's first wave id: no wave of the block has work past the queue
     if (((long long)blockIdx.x * blockDim.x >> 6) >= heavy_size) return;
+    const WaveId w = wave_id(blockDim.x >> 6);
     if (threadIdx.x == 0) st.n = 0;
     __syncthreads();
     unsigned my_deg = 0;
-    for (long long q = wave; q < heavy_size; q += nwaves) {
+    for (long long q = w.wave; q < heavy_size; q += w.n_waves) {
         const uint32_t u = heavy_queue[q];
         const uint64_t beg = row_off[u];
         const uint64_t end = row_off[u + 1];
-        for (uint64_t e = beg + lane; e < end; e += 64) {
+        for (uint64_t e = beg + w.lane; e < end; e += 64) {
             if (edge_filtered(etype, allowed_mask, e)) continue;
             my_deg += claim_and_stage(col[e], next_level, dist, row_off, st, next_frontier,
                                       next_count, capacity);
         }
     }
     stage_flush(st, next_frontier, next_count, capacity);
-    wave_add_degree(next_degree_sum, my_deg);
+    wave_add(next_degree_sum, my_deg);
 }
 
 // Edge-centric expansion for DENSE frontiers: one thread per edge, fully
@@ -257,8 +215,8 @@ __global__ void bfs_expand_edges_kernel(
             ++my_claims;
         }
     }
-    wave_add_degree(next_degree_sum, my_deg);
-    if (!build_frontier) wave_add_degree(next_count, my_claims);
+    wave_add(next_degree_sum, my_deg);
+    if (!build_frontier) wave_add(next_count, my_claims);
 }
 
 // Direction-optimized bottom-up step: every UNVISITED vertex probes its
@@ -297,8 +255,8 @@ __global__ void bfs_bottom_up_kernel(
         my_claims += claimed;
         my_open += allowed_edge && !claimed;
     }
-    wave_add_degree(next_count, my_claims);
-    wave_add_degree(open_count, my_open);
+    wave_add(next_count, my_claims);
+    wave_add(open_count, my_open);
 }
 
 // Rebuild a frontier from dist (nodes claimed at `level`): used when
@@ -319,7 +277,7 @@ __global__ void collect_frontier_kernel(
             my_deg += (unsigned)(row_off[i + 1] - row_off[i]);
         }
     }
-    wave_add_degree(degree_sum, my_deg);
+    wave_add(degree_sum, my_deg);
 }
 
 __global__ void seed_sources_kernel(
@@ -336,7 +294,7 @@ __global__ void seed_sources_kernel(
         frontier[i] = s;
         my_deg += (unsigned)(row_off[s + 1] - row_off[s]);
     }
-    wave_add_degree(degree_sum, my_deg);
+    wave_add(degree_sum, my_deg);
 }
 
 // dist[0..n) = UNVISITED with 16-byte stores, counters = 0.  `head` elements

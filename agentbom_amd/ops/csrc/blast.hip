@@ -1,6 +1,6 @@
 // Fused blast-radius reach counting on gfx950.
 //
-// Two entry points, same outputs (six counts and an overflow flag per
+// Three entry points, same outputs (six counts and an overflow flag per
 // package):
 //
 // abom_blast_counts_indexed — the engine's path.  A server's distinct
@@ -15,6 +15,11 @@
 // device; the kernels count the overflowed rows into one word, the only
 // thing the host reads.
 //
+// abom_blast_counts_indexed_sized — the same two passes when the host knows
+// only a bound on the package count: the count is a device word that an
+// earlier kernel of the stream writes, the grids are sized for the bound, and
+// the two counters reach pinned host memory through a copy on the stream.
+//
 // abom_blast_counts — for callers without an index (and the A/B knob
 // AGENT_BOM_BLAST_INDEX=0).  It replaced the torch sort/unique/bincount join
 // pipeline (gpu_engine.py _blast_counts_join — ~20 kernel launches per step)
@@ -27,7 +32,7 @@
 //
 // Zipf-head packages that overflow the LDS caps are flagged; the host
 // resolves just those with the sort-based path (hybrid, exact either way);
-// both entry points share the caps.
+// all entry points share the caps.
 // CDNA4 notes: one workgroup = 4 waves = 4 packages; LDS slice per wave =
 // (SRV_CAP + AG_CAP + CR_CAP + TL_CAP) * 4 B = 4.25 KiB -> 17 KiB/block,
 // sized so LDS is not the occupancy limiter (see cap comment below); the
@@ -35,7 +40,7 @@
 // segment tables, 6 KiB per wave -> 24 KiB/block.
 
 #include "abom_api.h"
-#include "abom_common.h"
+#include "abom_wave.h"
 
 namespace abom {
 
@@ -48,11 +53,6 @@ constexpr int AG_CAP = 256;
 constexpr int CR_CAP = 256;
 constexpr int TL_CAP = 512;
 constexpr int WAVES_PER_BLOCK = 4;
-
-__device__ __forceinline__ int wave_reduce_add(int v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 
 // Collect neighbors of `node` with edge type `want` into lds[cap]; returns
 // new count or -1 on overflow (count accumulated across calls).
@@ -145,8 +145,8 @@ __device__ __forceinline__ void distinct_count(
             if (db_flag && db_flag[v]) ++cnt_db;
         }
     }
-    *out_all = wave_reduce_add(cnt);
-    *out_db = wave_reduce_add(cnt_db);
+    *out_all = wave_sum(cnt);
+    *out_db = wave_sum(cnt_db);
 }
 
 __global__ void __launch_bounds__(256) blast_count_kernel(
@@ -166,12 +166,10 @@ __global__ void __launch_bounds__(256) blast_count_kernel(
     __shared__ uint32_t lds_cr[WAVES_PER_BLOCK][CR_CAP];
     __shared__ uint32_t lds_tl[WAVES_PER_BLOCK][TL_CAP];
 
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    const long long wave_global = (long long)blockIdx.x * WAVES_PER_BLOCK + wid;
-    const long long n_waves = (long long)gridDim.x * WAVES_PER_BLOCK;
+    const WaveId w = wave_id(WAVES_PER_BLOCK);
+    const int lane = w.lane, wid = w.wid;
 
-    for (long long p = wave_global; p < n; p += n_waves) {
+    for (long long p = w.wave; p < n; p += w.n_waves) {
         const uint32_t pkg = pkgs[p];
         bool overflow = false;
 
@@ -296,28 +294,9 @@ __global__ void __launch_bounds__(256) blast_index_fast_kernel(
             out_overflow[p] = 1;
         }
         // one atomic per wave and counter
-        const unsigned long long qmask = __ballot(multi);
-        if (qmask) {
-            const int leader = __ffsll((long long)qmask) - 1;
-            unsigned int qbase = 0;
-            if (lane == leader) qbase = atomicAdd(&counters[0], (unsigned int)__popcll(qmask));
-            qbase = __shfl(qbase, leader, 64);
-            if (multi) queue[qbase + __popcll(qmask & ((1ull << lane) - 1))] = (uint32_t)p;
-        }
-        const unsigned long long omask = __ballot(outside);
-        if (omask && lane == __ffsll((long long)omask) - 1)
-            atomicAdd(&counters[1], (unsigned int)__popcll(omask));
+        wave_queue_push(multi, (uint32_t)p, queue, &counters[0], lane);
+        wave_count_flag(outside, &counters[1], lane);
     }
-}
-
-__device__ __forceinline__ int wave_exclusive_scan(int v, int lane, int* total) {
-    int incl = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    *total = __shfl(incl, 63, 64);
-    return incl - v;
 }
 
 // Copy the index segments of the wave's servers into dst[0..total): entry i
@@ -327,12 +306,8 @@ __device__ __forceinline__ void gather_segments(
     const int* beg, const int* pref, int n_srv, int total,
     const uint32_t* __restrict__ reach_col, uint32_t* dst, int lane) {
     for (int i = lane; i < total; i += 64) {
-        int lo = 0, hi = n_srv;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (pref[mid] <= i) lo = mid; else hi = mid;
-        }
-        dst[i] = reach_col[beg[lo] + (i - pref[lo])];
+        const int s = segment_of(pref, n_srv, i);
+        dst[i] = reach_col[beg[s] + (i - pref[s])];
     }
 }
 
@@ -357,14 +332,12 @@ __global__ void __launch_bounds__(256) blast_index_wave_kernel(
     __shared__ uint32_t lds_cr[WAVES_PER_BLOCK][CR_CAP];
     __shared__ uint32_t lds_tl[WAVES_PER_BLOCK][TL_CAP];
 
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    const long long wave_global = (long long)blockIdx.x * WAVES_PER_BLOCK + wid;
-    const long long n_waves = (long long)gridDim.x * WAVES_PER_BLOCK;
+    const WaveId w = wave_id(WAVES_PER_BLOCK);
+    const int lane = w.lane, wid = w.wid;
     const long long n_queued = counters[0];
     uint32_t* srv = lds_srv[wid];
 
-    for (long long q = wave_global; q < n_queued; q += n_waves) {
+    for (long long q = w.wave; q < n_queued; q += w.n_waves) {
         const long long p = queue[q];
         const uint32_t pkg = pkgs[p];
         bool overflow = false;
@@ -445,6 +418,40 @@ __global__ void __launch_bounds__(256) blast_index_wave_kernel(
     }
 }
 
+// Both passes over `n` packages, or, with n_dev, over at most `n` packages of
+// which the device word says how many count: the grids are sized for `n` and
+// stride.
+static int launch_blast_index(
+    const void* pkgs, long long n, const void* n_dev,
+    const void* rev_off, const void* rev_col, const void* rev_et, int et_contains,
+    const void* reach_off, const void* reach_col, const void* reach_db,
+    long long row_base, long long num_rows,
+    const void* node_is_db_cred, const void* node_is_db_tool,
+    void* queue, void* counters, void* out_counts, void* out_overflow, hipStream_t s) {
+    const int block = 256;
+    hipLaunchKernelGGL(blast_index_fast_kernel, dim3(grid_for(n, block)), dim3(block), 0, s,
+                       (const uint32_t*)pkgs, n_dev ? 0ll : n, (const long long*)n_dev,
+                       (const uint64_t*)rev_off, (const uint32_t*)rev_col,
+                       (const uint8_t*)rev_et, (uint8_t)et_contains,
+                       (const int4*)reach_off, (const int2*)reach_db,
+                       (uint32_t)row_base, (uint32_t)num_rows,
+                       (uint32_t*)queue, (unsigned int*)counters,
+                       (uint32_t*)out_counts, (uint8_t*)out_overflow);
+    ABOM_CHECK(hipGetLastError());
+    // the queue length is known on the device only: size the grid for the
+    // worst case (every package queued) and let the waves stride over it
+    hipLaunchKernelGGL(blast_index_wave_kernel, dim3(grid_for(n, WAVES_PER_BLOCK)), dim3(block),
+                       0, s, (const uint32_t*)pkgs,
+                       (const uint64_t*)rev_off, (const uint32_t*)rev_col,
+                       (const uint8_t*)rev_et, (uint8_t)et_contains,
+                       (const int4*)reach_off, (const uint32_t*)reach_col,
+                       (uint32_t)row_base, (uint32_t)num_rows,
+                       (const uint8_t*)node_is_db_cred, (const uint8_t*)node_is_db_tool,
+                       (const uint32_t*)queue, (unsigned int*)counters,
+                       (uint32_t*)out_counts, (uint8_t*)out_overflow);
+    return (int)hipGetLastError();
+}
+
 }  // namespace abom
 
 extern "C" int abom_blast_counts_indexed(
@@ -457,36 +464,16 @@ extern "C" int abom_blast_counts_indexed(
     hipStream_t s = (hipStream_t)stream;
     ABOM_CHECK(hipMemsetAsync(counters, 0, 2 * sizeof(unsigned int), s));
     if (n <= 0) return 0;
-    const int block = 256;
-    hipLaunchKernelGGL(abom::blast_index_fast_kernel, dim3(abom::grid_for(n, block)),
-                       dim3(block), 0, s,
-                       (const uint32_t*)pkgs, n, (const long long*)nullptr,
-                       (const uint64_t*)rev_off, (const uint32_t*)rev_col,
-                       (const uint8_t*)rev_et, (uint8_t)et_contains,
-                       (const int4*)reach_off, (const int2*)reach_db,
-                       (uint32_t)row_base, (uint32_t)num_rows,
-                       (uint32_t*)queue, (unsigned int*)counters,
-                       (uint32_t*)out_counts, (uint8_t*)out_overflow);
-    ABOM_CHECK(hipGetLastError());
-    // the queue length is known on the device only: size the grid for the
-    // worst case (every package queued) and let the waves stride over it
-    hipLaunchKernelGGL(abom::blast_index_wave_kernel,
-                       dim3(abom::grid_for(n, abom::WAVES_PER_BLOCK)), dim3(block), 0, s,
-                       (const uint32_t*)pkgs,
-                       (const uint64_t*)rev_off, (const uint32_t*)rev_col,
-                       (const uint8_t*)rev_et, (uint8_t)et_contains,
-                       (const int4*)reach_off, (const uint32_t*)reach_col,
-                       (uint32_t)row_base, (uint32_t)num_rows,
-                       (const uint8_t*)node_is_db_cred, (const uint8_t*)node_is_db_tool,
-                       (const uint32_t*)queue, (unsigned int*)counters,
-                       (uint32_t*)out_counts, (uint8_t*)out_overflow);
-    return (int)hipGetLastError();
+    return abom::launch_blast_index(pkgs, n, nullptr, rev_off, rev_col, rev_et, et_contains,
+                                    reach_off, reach_col, reach_db, row_base, num_rows,
+                                    node_is_db_cred, node_is_db_tool, queue, counters,
+                                    out_counts, out_overflow, s);
 }
 
 // The same two passes over at most `n_cap` packages; the count itself is the
 // device word `n_dev`, which an earlier kernel of the stream writes.  The
-// grids are sized for n_cap and stride.  The counters reach `host_counters`
-// (pinned, two u32) through a copy on the stream; the caller waits for it.
+// counters reach `host_counters` (pinned, two u32) through a copy on the
+// stream; the caller waits for it.
 extern "C" int abom_blast_counts_indexed_sized(
     const void* pkgs, const void* n_dev, long long n_cap,
     const void* rev_off, const void* rev_col, const void* rev_et, int et_contains,
@@ -498,28 +485,11 @@ extern "C" int abom_blast_counts_indexed_sized(
     hipStream_t s = (hipStream_t)stream;
     ABOM_CHECK(hipMemsetAsync(counters, 0, 2 * sizeof(unsigned int), s));
     if (n_cap > 0) {
-        const int block = 256;
-        hipLaunchKernelGGL(abom::blast_index_fast_kernel, dim3(abom::grid_for(n_cap, block)),
-                           dim3(block), 0, s,
-                           (const uint32_t*)pkgs, 0ll, (const long long*)n_dev,
-                           (const uint64_t*)rev_off, (const uint32_t*)rev_col,
-                           (const uint8_t*)rev_et, (uint8_t)et_contains,
-                           (const int4*)reach_off, (const int2*)reach_db,
-                           (uint32_t)row_base, (uint32_t)num_rows,
-                           (uint32_t*)queue, (unsigned int*)counters,
-                           (uint32_t*)out_counts, (uint8_t*)out_overflow);
-        ABOM_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(abom::blast_index_wave_kernel,
-                           dim3(abom::grid_for(n_cap, abom::WAVES_PER_BLOCK)), dim3(block), 0, s,
-                           (const uint32_t*)pkgs,
-                           (const uint64_t*)rev_off, (const uint32_t*)rev_col,
-                           (const uint8_t*)rev_et, (uint8_t)et_contains,
-                           (const int4*)reach_off, (const uint32_t*)reach_col,
-                           (uint32_t)row_base, (uint32_t)num_rows,
-                           (const uint8_t*)node_is_db_cred, (const uint8_t*)node_is_db_tool,
-                           (const uint32_t*)queue, (unsigned int*)counters,
-                           (uint32_t*)out_counts, (uint8_t*)out_overflow);
-        ABOM_CHECK(hipGetLastError());
+        const int rc = abom::launch_blast_index(
+            pkgs, n_cap, n_dev, rev_off, rev_col, rev_et, et_contains, reach_off, reach_col,
+            reach_db, row_base, num_rows, node_is_db_cred, node_is_db_tool, queue, counters,
+            out_counts, out_overflow, s);
+        if (rc != 0) return rc;
     }
     ABOM_CHECK(hipMemcpyAsync(host_counters, counters, 2 * sizeof(unsigned int),
                               hipMemcpyDeviceToHost, s));
@@ -534,10 +504,8 @@ extern "C" int abom_blast_counts(
     const void* node_is_db_cred, const void* node_is_db_tool,
     void* out_counts, void* out_overflow, void* stream) {
     const int block = 256;
-    long long blocks = (n + abom::WAVES_PER_BLOCK - 1) / abom::WAVES_PER_BLOCK;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(abom::blast_count_kernel, dim3((int)blocks), dim3(block), 0,
+    hipLaunchKernelGGL(abom::blast_count_kernel,
+                       dim3(abom::grid_for(n, abom::WAVES_PER_BLOCK)), dim3(block), 0,
                        (hipStream_t)stream,
                        (const uint32_t*)pkgs, n,
                        (const uint64_t*)rev_off, (const uint32_t*)rev_col,

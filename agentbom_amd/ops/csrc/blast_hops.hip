@@ -33,7 +33,7 @@
 // waves per SIMD.  Larger caps trade occupancy for fallback rate.
 
 #include "abom_api.h"
-#include "abom_common.h"
+#include "abom_wave.h"
 
 namespace abom {
 
@@ -74,16 +74,6 @@ __device__ __forceinline__ int2 hop_segment(const HopIndex& ix, uint32_t node) {
                                     : make_int2(off.y, off.z - off.y);
 }
 
-__device__ __forceinline__ int hops_exclusive_scan(int v, int lane, int* total) {
-    int incl = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
-    }
-    *total = __shfl(incl, 63, 64);
-    return incl - v;
-}
-
 // Append this wave's candidates (one per lane with `valid`) that are neither
 // in list[0..n) nor held by an earlier lane.  False, with nothing stored, when
 // the list would pass `cap`: the bound is checked before any store.
@@ -122,7 +112,7 @@ __device__ __forceinline__ bool expand_append(
         int2 seg = make_int2(0, 0);
         if (i < i_end) seg = hop_segment<KIND>(ix, items[i]);
         int total;
-        const int pref = hops_exclusive_scan(seg.y, lane, &total);
+        const int pref = wave_exclusive_scan(seg.y, lane, &total);
         t_beg[lane] = seg.x;
         t_pref[lane] = pref;
         __builtin_amdgcn_wave_barrier();
@@ -132,12 +122,8 @@ __device__ __forceinline__ bool expand_append(
             const bool valid = j < total;
             uint32_t v = 0;
             if (valid) {
-                int lo = 0, hi = n_items;
-                while (hi - lo > 1) {
-                    const int mid = (lo + hi) >> 1;
-                    if (t_pref[mid] <= j) lo = mid; else hi = mid;
-                }
-                v = col[t_beg[lo] + (j - t_pref[lo])];
+                const int s = segment_of(t_pref, n_items, j);
+                v = col[t_beg[s] + (j - t_pref[s])];
             }
             if (!append_distinct(dst, n_dst, cap, v, valid, stage, lane)) return false;
         }
@@ -237,14 +223,7 @@ __global__ void __launch_bounds__(256) blast_hops_fast_kernel(
                            make_int4(0, 0, 0, 0), 0, 1, false);
         }
         // one atomic per wave
-        const unsigned long long qmask = __ballot(queued);
-        if (qmask) {
-            const int leader = __ffsll((long long)qmask) - 1;
-            unsigned int qbase = 0;
-            if (lane == leader) qbase = atomicAdd(&counters[0], (unsigned int)__popcll(qmask));
-            qbase = __shfl(qbase, leader, 64);
-            if (queued) queue[qbase + __popcll(qmask & ((1ull << lane) - 1))] = (uint32_t)p;
-        }
+        wave_queue_push(queued, (uint32_t)p, queue, &counters[0], lane);
     }
 }
 
@@ -264,10 +243,8 @@ __global__ void __launch_bounds__(256) blast_hops_wave_kernel(
     __shared__ int lds_beg[HOPS_WAVES][64];
     __shared__ int lds_pref[HOPS_WAVES][64];
 
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    const long long wave_global = (long long)blockIdx.x * HOPS_WAVES + wid;
-    const long long n_waves = (long long)gridDim.x * HOPS_WAVES;
+    const WaveId w = wave_id(HOPS_WAVES);
+    const int lane = w.lane, wid = w.wid;
     const long long n_queued = counters[0];
     uint32_t* srv = lds_srv[wid];
     uint32_t* ag = lds_ag[wid];
@@ -276,7 +253,7 @@ __global__ void __launch_bounds__(256) blast_hops_wave_kernel(
     int* t_beg = lds_beg[wid];
     int* t_pref = lds_pref[wid];
 
-    for (long long q = wave_global; q < n_queued; q += n_waves) {
+    for (long long q = w.wave; q < n_queued; q += w.n_waves) {
         const long long p = queue[q];
         const uint32_t pkg = pkgs[p];
         int n_srv = 0, n_ag = 0, n_cr = 0;

@@ -25,7 +25,7 @@
 // of this file: C++, one device->host scalar read per iteration / level.
 
 #include "abom_api.h"
-#include "abom_common.h"
+#include "abom_wave.h"
 
 namespace abom {
 
@@ -35,18 +35,6 @@ constexpr uint64_t CENTRALITY_HEAVY_DEGREE = 64;
 
 constexpr int CEN_BLOCK = 256;                 // 4 waves
 constexpr int CEN_WAVES = CEN_BLOCK / 64;
-
-// Fixed-tree wave sum; the total lands in lane 0.
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// One integer atomic per wave (same shape as bfs.hip's wave_add_degree).
-__device__ __forceinline__ void wave_count(unsigned int* dst, unsigned v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, v);
-}
 
 // Grid for one-wave-per-row kernels over `rows` heavy rows.
 inline int heavy_grid(long long rows) { return grid_for(rows * 64, CEN_BLOCK); }
@@ -64,8 +52,8 @@ inline int heavy_grid(long long rows) { return grid_for(rows * 64, CEN_BLOCK); }
 __device__ __forceinline__ void block_store_partials(double a, double b,
                                                      double* __restrict__ partial_pair) {
     __shared__ double sh[2 * CEN_WAVES];
-    a = wave_sum_f64(a);
-    b = wave_sum_f64(b);
+    a = wave_sum(a);
+    b = wave_sum(b);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         sh[2 * wave] = a;
@@ -146,19 +134,18 @@ __global__ __launch_bounds__(CEN_BLOCK) void pagerank_pull_heavy_kernel(
     const double* __restrict__ rank, const double* __restrict__ contrib,
     double* __restrict__ new_rank, double* __restrict__ new_contrib,
     double* __restrict__ partials) {
-    const int lane = threadIdx.x & 63;
-    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
+    const WaveId w = wave_id(blockDim.x >> 6);
+    const int lane = w.lane;
     const double teleport = (1.0 - damping) / (double)num_nodes;
     const double dangling_share = damping * scalars[1] / (double)num_nodes;
     double l1 = 0.0, dangling = 0.0;  // carried by lane 0 only
-    for (long long q = wave; q < num_heavy; q += nwaves) {
+    for (long long q = w.wave; q < num_heavy; q += w.n_waves) {
         const long long v = heavy_rows[q];
         const uint64_t beg = rev_off[v];
         const uint64_t end = rev_off[v + 1];
         double pulled = 0.0;
         for (uint64_t e = beg + lane; e < end; e += 64) pulled += contrib[rev_col[e]];
-        pulled = wave_sum_f64(pulled);
+        pulled = wave_sum(pulled);
         if (lane == 0)
             pagerank_store(v, pulled, teleport, damping, dangling_share, out_degree, rank,
                            new_rank, new_contrib, l1, dangling);
@@ -176,8 +163,8 @@ __global__ __launch_bounds__(64) void pagerank_finalize_kernel(
         a += partials[2 * (size_t)i];
         b += partials[2 * (size_t)i + 1];
     }
-    a = wave_sum_f64(a);
-    b = wave_sum_f64(b);
+    a = wave_sum(a);
+    b = wave_sum(b);
     if (threadIdx.x == 0) {
         scalars[0] = a;
         scalars[1] = b;
@@ -235,7 +222,7 @@ __global__ __launch_bounds__(CEN_BLOCK) void brandes_forward_kernel(
             ++claims;
         }
     }
-    wave_count(discovered, claims);
+    wave_add(discovered, claims);
 }
 
 // Forward level L, wave per heavy row (same race argument as above).
@@ -246,12 +233,11 @@ __global__ __launch_bounds__(CEN_BLOCK) void brandes_forward_heavy_kernel(
     uint32_t level, uint32_t* __restrict__ dist, double* __restrict__ sigma,
     unsigned int* __restrict__ discovered) {
     const uint64_t base = (uint64_t)blockIdx.y * (uint64_t)num_nodes;
-    const int lane = threadIdx.x & 63;
-    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
+    const WaveId w = wave_id(blockDim.x >> 6);
+    const int lane = w.lane;
     const uint32_t prev = level - 1;
     unsigned claims = 0;  // lane 0 only
-    for (long long q = wave; q < num_heavy; q += nwaves) {
+    for (long long q = w.wave; q < num_heavy; q += w.n_waves) {
         const uint64_t v = heavy_rows[q];
         if (dist[base + v] != ABOM_UNVISITED) continue;  // wave-uniform
         const uint64_t beg = rev_off[v];
@@ -266,7 +252,7 @@ __global__ __launch_bounds__(CEN_BLOCK) void brandes_forward_heavy_kernel(
                 found = true;
             }
         }
-        paths = wave_sum_f64(paths);
+        paths = wave_sum(paths);
         const bool any_found = __ballot(found) != 0ull;
         if (lane == 0 && any_found) {
             dist[base + v] = level;
@@ -312,11 +298,10 @@ __global__ __launch_bounds__(CEN_BLOCK) void brandes_backward_heavy_kernel(
     uint32_t level, const uint32_t* __restrict__ dist, const double* __restrict__ sigma,
     double* __restrict__ delta) {
     const uint64_t base = (uint64_t)blockIdx.y * (uint64_t)num_nodes;
-    const int lane = threadIdx.x & 63;
-    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
+    const WaveId w = wave_id(blockDim.x >> 6);
+    const int lane = w.lane;
     const uint32_t next = level + 1;
-    for (long long q = wave; q < num_heavy; q += nwaves) {
+    for (long long q = w.wave; q < num_heavy; q += w.n_waves) {
         const uint64_t v = heavy_rows[q];
         if (dist[base + v] != level) continue;  // wave-uniform
         const uint64_t beg = fwd_off[v];
@@ -328,7 +313,7 @@ __global__ __launch_bounds__(CEN_BLOCK) void brandes_backward_heavy_kernel(
             const uint64_t w = base + fwd_col[e];
             if (dist[w] == next) dep += sv / sigma[w] * (1.0 + delta[w]);
         }
-        dep = wave_sum_f64(dep);
+        dep = wave_sum(dep);
         if (lane == 0) delta[base + v] = dep;
     }
 }

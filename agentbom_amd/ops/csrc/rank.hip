@@ -18,7 +18,7 @@
 // __syncthreads in the inner loop).  Four small launches replace the
 // multi-kernel rocprim onesweep pipeline.
 #include "abom_api.h"
-#include "abom_common.h"
+#include "abom_wave.h"
 
 namespace {
 
@@ -80,15 +80,11 @@ __global__ void rank_scan_blocks_kernel(int* __restrict__ hist,
         const int idx = t + lane;
         const int v = (idx < nblocks)
             ? hist[(long long)idx * RANK_BINS + bin] : 0;
-        int x = v;  // wave inclusive scan
-        #pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int y = __shfl_up(x, off);
-            if (lane >= off) x += y;
-        }
+        int total;  // of the tile, in every lane
+        const int before = abom::wave_exclusive_scan(v, lane, &total);
         if (idx < nblocks)
-            hist[(long long)idx * RANK_BINS + bin] = x - v + carry;
-        carry += __shfl(x, 63);  // tile total, broadcast to all lanes
+            hist[(long long)idx * RANK_BINS + bin] = before + carry;
+        carry += total;
     }
     if (lane == 0) bin_total[bin] = carry;
 }

@@ -33,7 +33,7 @@
 // per level, the frontier count read through pinned host memory.
 
 #include "abom_api.h"
-#include "abom_common.h"
+#include "abom_wave.h"
 
 namespace abom {
 
@@ -52,55 +52,17 @@ constexpr uint64_t REACH_HEAVY_DEG = ABOM_REACH_HEAVY_DEG;
 // Entries of the per-block LDS append queue (16 KiB).
 constexpr unsigned REACH_STAGE = 4096;
 
-// Per-block LDS queue of next-frontier entries.  `n` counts the appends since
-// the last flush and may pass REACH_STAGE: those went straight to the queue.
-struct ReachStage {
-    uint32_t e[REACH_STAGE];
-    unsigned n;
-    unsigned base;
-};
-
-__device__ __forceinline__ void reach_stage_push(
-    uint32_t entry, ReachStage& st, uint32_t* __restrict__ next_queue,
-    unsigned int* __restrict__ next_count, long long capacity) {
-    const unsigned slot = atomicAdd(&st.n, 1u);
-    if (slot < REACH_STAGE) {
-        st.e[slot] = entry;
-    } else {
-        const unsigned idx = atomicAdd(next_count, 1u);
-        if ((long long)idx < capacity) next_queue[idx] = entry;
-    }
-}
-
-// Whole block: one global atomic for the staged entries, then a coalesced
-// copy.  Barriers inside; the caller resets st.n before the next push.
-__device__ __forceinline__ void reach_stage_flush(
-    ReachStage& st, uint32_t* __restrict__ next_queue,
-    unsigned int* __restrict__ next_count, long long capacity) {
-    __syncthreads();
-    const unsigned n = st.n < REACH_STAGE ? st.n : REACH_STAGE;
-    if (threadIdx.x == 0 && n) st.base = atomicAdd(next_count, n);
-    __syncthreads();
-    if (n) {
-        const unsigned base = st.base;
-        for (unsigned i = threadIdx.x; i < n; i += blockDim.x) {
-            const unsigned idx = base + i;
-            if ((long long)idx < capacity) next_queue[idx] = st.e[i];
-        }
-    }
-}
-
 // Offer `bits` of word k to neighbour w.
 __device__ __forceinline__ void reach_offer(
     uint32_t w, uint32_t k, uint32_t W, uint64_t bits,
-    const uint64_t* __restrict__ seen, uint64_t* __restrict__ nxt, ReachStage& st,
-    uint32_t* __restrict__ next_queue, unsigned int* __restrict__ next_count,
-    long long capacity) {
+    const uint64_t* __restrict__ seen, uint64_t* __restrict__ nxt,
+    BlockStage<REACH_STAGE>& st, uint32_t* __restrict__ next_queue,
+    unsigned int* __restrict__ next_count, long long capacity) {
     const uint32_t idx = w * W + k;
     const uint64_t nb = bits & ~seen[idx];
     if (!nb) return;
     const uint64_t old = atomicOr((unsigned long long*)&nxt[idx], (unsigned long long)nb);
-    if (old == 0) reach_stage_push(idx, st, next_queue, next_count, capacity);
+    if (old == 0) stage_push(idx, st, next_queue, next_count, capacity);
 }
 
 // nxt[s*W + j/64] |= 1 << (j%64) for source j of the pass; the lane that set
@@ -132,7 +94,7 @@ __global__ __launch_bounds__(256) void reach_expand_kernel(
     uint32_t* __restrict__ next_queue, unsigned int* __restrict__ next_count,
     uint32_t* __restrict__ heavy_queue, unsigned int* __restrict__ heavy_count,
     long long capacity) {
-    __shared__ ReachStage st;
+    __shared__ BlockStage<REACH_STAGE> st;
     const long long stride = (long long)gridDim.x * blockDim.x;
     const long long rounds = (queue_size + stride - 1) / stride;
     for (long long r = 0; r < rounds; ++r) {
@@ -159,7 +121,7 @@ __global__ __launch_bounds__(256) void reach_expand_kernel(
                 }
             }
         }
-        reach_stage_flush(st, next_queue, next_count, capacity);
+        stage_flush(st, next_queue, next_count, capacity);
     }
 }
 
@@ -172,30 +134,28 @@ __global__ __launch_bounds__(256) void reach_expand_heavy_kernel(
     const uint64_t* __restrict__ seen, uint64_t* __restrict__ cur, uint64_t* __restrict__ nxt,
     uint32_t* __restrict__ next_queue, unsigned int* __restrict__ next_count,
     long long capacity) {
-    __shared__ ReachStage st;
+    __shared__ BlockStage<REACH_STAGE> st;
     long long heavy_size = *heavy_size_ptr;
     if (heavy_size > capacity) heavy_size = capacity;
-    const int lane = threadIdx.x & 63;
-    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
+    const WaveId w = wave_id(blockDim.x >> 6);
     // the block's first wave id: no wave of the block has work past the queue
     if (((long long)blockIdx.x * blockDim.x >> 6) >= heavy_size) return;
     if (threadIdx.x == 0) st.n = 0;
     __syncthreads();
-    for (long long q = wave; q < heavy_size; q += nwaves) {
+    for (long long q = w.wave; q < heavy_size; q += w.n_waves) {
         const uint32_t e = heavy_queue[q];
         const uint32_t v = e / W;
         const uint32_t k = e - v * W;
         const uint64_t bits = cur[e];
-        if (lane == 0) cur[e] = 0;
+        if (w.lane == 0) cur[e] = 0;
         const uint64_t beg = row_off[v];
         const uint64_t end = row_off[v + 1];
-        for (uint64_t x = beg + lane; x < end; x += 64) {
+        for (uint64_t x = beg + w.lane; x < end; x += 64) {
             if (edge_filtered(etype, allowed_mask, x)) continue;
             reach_offer(col[x], k, W, bits, seen, nxt, st, next_queue, next_count, capacity);
         }
     }
-    reach_stage_flush(st, next_queue, next_count, capacity);
+    stage_flush(st, next_queue, next_count, capacity);
 }
 
 // The queue size is read from the device, so the launch need not wait for the

@@ -105,6 +105,20 @@ def star() -> ReachGraph:
     return ReachGraph("star", 303, edges, [0, 301], targets, dist)
 
 
+# REACH_STAGE (csrc/reach_sets.hip, 4096 entries of a block's LDS append
+# queue) less one, exactly, and one more
+STAGE_STAR_LEAVES = (4095, 4096, 4097)
+
+
+def stage_star(leaves: int) -> ReachGraph:
+    """Hub 0 with ``leaves`` distinct leaves, every leaf a target: one wave of
+    the wave-per-row expand pushes all of them through one block's LDS queue,
+    the ones past its capacity straight to the global queue."""
+    ids = list(range(1, leaves + 1))
+    return ReachGraph(f"stage_star_{leaves}", leaves + 1, [(0, leaf, 0) for leaf in ids],
+                      [0], ids, [[1] for _ in ids])
+
+
 def no_in_edges() -> ReachGraph:
     """Target 2 has out-edges only: its row is all 255."""
     return ReachGraph("no_in_edges", 3, [(0, 1, 0), (2, 1, 0)], [0, 1], [2, 1],

@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 import torch
 from reach_sets_graphs import (
-    DEPTHS, ESTATE_ARGS, GRAPHS, NO, SOURCE_COUNTS, edited_demo_graph, estate_agents,
-    random_graph, random_sources, star,
+    DEPTHS, ESTATE_ARGS, GRAPHS, NO, SOURCE_COUNTS, STAGE_STAR_LEAVES, edited_demo_graph,
+    estate_agents, random_graph, random_sources, stage_star, star,
 )
 
 from agentbom_amd.graph.builder import build_unified_graph_from_report
@@ -60,6 +60,16 @@ def test_kernel_equals_oracle_on_hand_built_graphs(make, depth):
     _check(got, want)
     assert isinstance(ws["levels"], int) and isinstance(ws["passes"], int)
     assert ws["passes"] == 1 and 0 <= ws["levels"] <= depth
+
+
+@pytest.mark.parametrize("leaves", STAGE_STAR_LEAVES)
+def test_one_block_stages_a_row_around_its_queue_capacity(leaves):
+    g = stage_star(leaves)
+    csr = g.csr()
+    want = cpu_ref.reach_hops(*csr[:2], g.sources, g.targets, g.num_nodes, etype=csr[2],
+                              allowed_mask=g.mask, max_depth=1)
+    assert np.array_equal(want, g.expected(1)) and (want == 1).all()
+    _check(_run(csr, g.sources, g.targets, g.num_nodes, g.mask, 1), want)
 
 
 @pytest.fixture(scope="module")
