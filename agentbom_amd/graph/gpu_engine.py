@@ -16,7 +16,13 @@ construction) and stays resident in HBM3E.  On top of it:
                          AGENT_BOM_MATCH_TILED=0 probes global memory
                          instead); AGENT_BOM_MATCH_BY_WINDOW=0, or an estate
                          without a dedup layout, keeps the row kernel there
-- ``dependency_reach()`` multi-source BFS from all agents (ops/csrc/bfs.hip)
+- ``dependency_reach()`` multi-source BFS from all agents (ops/csrc/bfs.hip).
+                         Its dense level is a bottom-up pass over a parent
+                         index (``native.bfs_parent_index``: per vertex the
+                         first allowed in-edge of its reverse row, built once
+                         with the CSR for the mask of the reach walk);
+                         AGENT_BOM_BFS_PARENT_INDEX=0 walks the reverse rows
+                         instead
 - ``agent_reach()``      hop count per (target, agent) for a set of agents:
                          bit-parallel multi-source BFS, 64 agents per 64-bit
                          word (ops/csrc/reach_sets.hip)
@@ -462,6 +468,10 @@ def rank_order(torch, scores):
     return (skey.to(torch.int64)) & ((1 << bits) - 1)
 
 
+# edge types dependency_reach() walks
+_REACH_MASK = (1 << ET_USES) | (1 << ET_CONTAINS) | (1 << ET_HAS_CRED) | (1 << ET_PROVIDES_TOOL)
+
+
 class EstateEngine:
     """Device-resident estate + advisory arena + the findings pipeline."""
 
@@ -543,6 +553,13 @@ class EstateEngine:
         self.reach_index = build_reach_index(
             torch, src, dst, et, estate.server_base, estate.n_servers,
             self.node_is_db_cred, self.node_is_db_tool) if self.use_gpu else None
+        # parent index of the reach BFS's bottom-up pass: one word per vertex
+        # of (rev, the mask of dependency_reach), same lifetime; 4N bytes
+        self.bfs_parent_index = None
+        if self.use_gpu:
+            from agentbom_amd.ops import native
+
+            self.bfs_parent_index = native.bfs_parent_index(self.rev, _REACH_MASK, self.N)
         # per-agent server index of the multi-hop expansion: same lifetime
         self._hops_ws: dict = {}
         self.agent_index = build_agent_index(
@@ -620,7 +637,7 @@ class EstateEngine:
         """u32 hop distance from the nearest agent, per node (multi-source BFS).
 
         ``begun``: :meth:`_reach_begin` has been called for this pass."""
-        mask = (1 << ET_USES) | (1 << ET_CONTAINS) | (1 << ET_HAS_CRED) | (1 << ET_PROVIDES_TOOL)
+        mask = _REACH_MASK
         if self.use_gpu:
             from agentbom_amd.ops import native
 
@@ -629,6 +646,7 @@ class EstateEngine:
                 etype=self.fwd["etype"], allowed_mask=mask, workspace=self._bfs_ws,
                 edge_src=self.fwd["src"], rev=self.rev,
                 begun=begun, sources_degree=self._agents_degree,
+                parent_index=self.bfs_parent_index,
             )
         from agentbom_amd.ops import cpu_ref
 

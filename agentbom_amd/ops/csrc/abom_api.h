@@ -45,8 +45,8 @@ int abom_match_by_window_tiled(
     const void* s_key, const void* s_row,
     void* out_pairs, void* out_count, long long capacity, void* stream);
 
-// bfs.hip (abom_bfs_run and abom_bfs_run_ex return the number of levels run
-// or a negated hipError_t)
+// bfs.hip (abom_bfs_run, abom_bfs_run_ex and abom_bfs_run_indexed return the
+// number of levels run or a negated hipError_t)
 int abom_bfs_expand(
     const void* row_off, const void* col, const void* etype, unsigned int allowed_mask,
     const void* frontier, long long frontier_size, void* dist, unsigned int next_level,
@@ -81,6 +81,34 @@ int abom_bfs_run_ex(
     void* frontier_a, void* frontier_b, void* heavy_queue, void* counters,
     int max_levels, const void* edge_src, long long num_edges,
     const void* rev_off, const void* rev_col, const void* rev_et,
+    int begun, long long sources_degree, void* host_counters, void* stream);
+// the parent index of the bottom-up pass, built once per (reverse CSR,
+// allowed_mask): first_parent u32 [num_nodes] = 0xFFFFFFFF for a vertex
+// without an allowed in-edge, else the source of the first allowed in-edge of
+// its reverse row in bits 0-30 and bit 31 set when the row holds another
+// allowed in-edge; num_nodes >= 2^31 - 1 is refused (hipErrorInvalidValue)
+int abom_bfs_parent_index(
+    const void* rev_off, const void* rev_col, const void* rev_et, unsigned int allowed_mask,
+    long long num_nodes, void* first_parent, void* stream);
+// one bottom-up pass at cur_level over the reverse rows, or over the parent
+// index with the rows behind it: *next_count += vertices claimed, *open_count
+// += vertices left unvisited that have an allowed in-edge
+int abom_bfs_bottom_up(
+    const void* rev_off, const void* rev_col, const void* rev_et, unsigned int allowed_mask,
+    long long num_nodes, void* dist, unsigned int cur_level,
+    void* next_count, void* open_count, void* stream);
+int abom_bfs_bottom_up_indexed(
+    const void* rev_off, const void* rev_col, const void* rev_et, unsigned int allowed_mask,
+    long long num_nodes, void* dist, unsigned int cur_level, const void* first_parent,
+    void* next_count, void* open_count, void* stream);
+// abom_bfs_run_ex with the parent index of (rev, allowed_mask) for its
+// bottom-up levels; first_parent is nullable (then it is abom_bfs_run_ex)
+int abom_bfs_run_indexed(
+    const void* row_off, const void* col, const void* etype, unsigned int allowed_mask,
+    const void* sources, long long n_sources, void* dist, long long num_nodes,
+    void* frontier_a, void* frontier_b, void* heavy_queue, void* counters,
+    int max_levels, const void* edge_src, long long num_edges,
+    const void* rev_off, const void* rev_col, const void* rev_et, const void* first_parent,
     int begun, long long sources_degree, void* host_counters, void* stream);
 
 // reach_sets.hip (one pass of per-source reach for n_sources <= 64 * words

@@ -18,6 +18,13 @@
 //   expanded by whole waves from a secondary queue filled in pass 1.
 // - dense levels (frontier edges > 1/8 of all edges) switch to a pass over
 //   all edges or, with a reverse CSR, a bottom-up pass over all vertices.
+// - with a parent index (abom_bfs_parent_index: per vertex the first allowed
+//   in-edge of its reverse row, built once per reverse CSR and mask) the
+//   bottom-up pass reads dist and one index word per vertex, four vertices
+//   per thread with 16-byte loads, and gathers dist[parent]; the reverse row
+//   is walked only when that parent is outside the frontier and the row has
+//   another allowed in-edge.  The row walk alone is a chain of four
+//   dependent loads per vertex over 64-bit offsets, type bytes and columns.
 // - a block of bfs_expand_kernel or bfs_expand_heavy_kernel stages its claims
 //   in an LDS queue and reserves their slots of the next frontier with ONE
 //   atomic per flush: the frontier counter is a single word, and a returning
@@ -31,7 +38,8 @@
 //   caller that overlaps the BFS with other work can put the 4N-byte fill
 //   ahead of that work instead of beside it.
 //
-// The host-side level loop is abom_bfs_run_ex at the end of this file (C++,
+// The host-side level loop is abom_bfs_run_indexed at the end of this file
+// (abom_bfs_run_ex and abom_bfs_run are that loop without an index; C++,
 // one sync per level, counts read into pinned host memory when the caller
 // passes some; the degree sum of the sources is read only when the caller
 // does not know it).
@@ -259,6 +267,144 @@ __global__ void bfs_bottom_up_kernel(
     wave_add(open_count, my_open);
 }
 
+// The parent index of the bottom-up pass: which vertex has which allowed
+// parent is a property of the reverse CSR and the edge mask, not of a
+// traversal.  first_parent[v] = PARENT_NONE when v has no allowed in-edge;
+// else bits 0-30 = the source of the first allowed in-edge in reverse-row
+// order, PARENT_MORE set when the row holds a second allowed in-edge (from
+// the same parent or another).
+constexpr uint32_t PARENT_NONE = 0xFFFFFFFFu;
+constexpr uint32_t PARENT_MORE = 0x80000000u;
+
+__global__ void bfs_parent_index_kernel(
+    const uint64_t* __restrict__ rev_off,
+    const uint32_t* __restrict__ rev_col,
+    const uint8_t* __restrict__ rev_et,
+    uint32_t allowed_mask,
+    long long num_nodes,
+    uint32_t* __restrict__ first_parent) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v < num_nodes;
+         v += stride) {
+        const uint64_t end = rev_off[v + 1];
+        uint32_t entry = PARENT_NONE;
+        for (uint64_t e = rev_off[v]; e < end; ++e) {
+            if (edge_filtered(rev_et, allowed_mask, e)) continue;
+            if (entry != PARENT_NONE) {
+                entry |= PARENT_MORE;
+                break;
+            }
+            entry = rev_col[e];
+        }
+        first_parent[v] = entry;
+    }
+}
+
+// One vertex of the indexed bottom-up pass, after its first parent missed:
+// walk the reverse row with the mask, as bfs_bottom_up_kernel does.
+__device__ __forceinline__ bool bottom_up_walk_row(
+    long long v, const uint64_t* __restrict__ rev_off, const uint32_t* __restrict__ rev_col,
+    const uint8_t* __restrict__ rev_et, uint32_t allowed_mask,
+    const uint32_t* dist, uint32_t cur_level) {
+    const uint64_t end = rev_off[v + 1];
+    for (uint64_t e = rev_off[v]; e < end; ++e) {
+        if (edge_filtered(rev_et, allowed_mask, e)) continue;
+        if (dist[rev_col[e]] == cur_level) return true;
+    }
+    return false;
+}
+
+// A single vertex of the indexed pass: the words of dist before and after
+// its 16-byte body; counts like the body does.
+__device__ __forceinline__ void bottom_up_indexed_one(
+    long long v, const uint32_t* __restrict__ first_parent,
+    const uint64_t* __restrict__ rev_off, const uint32_t* __restrict__ rev_col,
+    const uint8_t* __restrict__ rev_et, uint32_t allowed_mask,
+    uint32_t* dist, uint32_t cur_level, unsigned& claims, unsigned& open) {
+    const uint32_t d = dist[v];
+    const uint32_t fp = first_parent[v];
+    if (d != ABOM_UNVISITED || fp == PARENT_NONE) return;
+    bool hit = dist[fp & ~PARENT_MORE] == cur_level;
+    if (!hit && (fp & PARENT_MORE))
+        hit = bottom_up_walk_row(v, rev_off, rev_col, rev_et, allowed_mask, dist, cur_level);
+    if (hit) dist[v] = cur_level + 1;
+    claims += hit;
+    open += !hit;
+}
+
+// The bottom-up pass over the parent index.  A thread takes four consecutive
+// vertices of the 16-byte-aligned body of dist (`head` words come before it,
+// `n4` uint4 make it up, as in bfs_fill_kernel): it loads their dist and
+// first_parent words together, then gathers the four dist[parent] together,
+// then stores the four words back at once when it claimed any.  Only the
+// thread of v writes dist[v], so writing back an unclaimed word as read is
+// exact.  A vertex that needs no gather reads its own dist word in its place.
+// The reverse row is walked only when the first parent missed and the entry
+// says there is another allowed in-edge.  `fp_vec`: first_parent + head is
+// 16-byte aligned too.
+__global__ __launch_bounds__(256) void bfs_bottom_up_indexed_kernel(
+    const uint32_t* __restrict__ first_parent,
+    const uint64_t* __restrict__ rev_off,
+    const uint32_t* __restrict__ rev_col,
+    const uint8_t* __restrict__ rev_et,
+    uint32_t allowed_mask,
+    long long num_nodes, long long head, long long n4, int fp_vec,
+    uint32_t* dist,  // read at the parents, written at the thread's own vertices
+    uint32_t cur_level,
+    unsigned int* __restrict__ next_count,
+    unsigned int* __restrict__ open_count) {
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    unsigned my_claims = 0;
+    unsigned my_open = 0;  // left unvisited, yet with an index entry
+    uint4* body = reinterpret_cast<uint4*>(dist + head);
+    const uint32_t* __restrict__ fp_body = first_parent + head;
+    for (long long i = tid; i < n4; i += stride) {
+        const long long v0 = head + 4 * i;
+        const uint4 d4 = body[i];
+        uint4 f4;
+        if (fp_vec) {
+            f4 = reinterpret_cast<const uint4*>(fp_body)[i];
+        } else {
+            f4 = make_uint4(fp_body[4 * i], fp_body[4 * i + 1], fp_body[4 * i + 2],
+                            fp_body[4 * i + 3]);
+        }
+        uint32_t d[4] = {d4.x, d4.y, d4.z, d4.w};
+        const uint32_t f[4] = {f4.x, f4.y, f4.z, f4.w};
+        bool want[4];
+        uint32_t g[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            // & not &&: no branch between the loads
+            want[k] = (d[k] == ABOM_UNVISITED) & (f[k] != PARENT_NONE);
+            g[k] = dist[want[k] ? (long long)(f[k] & ~PARENT_MORE) : v0 + k];
+        }
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!want[k]) continue;
+            bool hit = g[k] == cur_level;
+            if (!hit && (f[k] & PARENT_MORE))
+                hit = bottom_up_walk_row(v0 + k, rev_off, rev_col, rev_et, allowed_mask, dist,
+                                         cur_level);
+            if (hit) d[k] = cur_level + 1;
+            any |= hit;
+            my_claims += hit;
+            my_open += !hit;
+        }
+        if (any) body[i] = make_uint4(d[0], d[1], d[2], d[3]);
+    }
+    const long long tail = head + 4 * n4;  // first vertex after the body
+    if (tid < head)
+        bottom_up_indexed_one(tid, first_parent, rev_off, rev_col, rev_et, allowed_mask, dist,
+                              cur_level, my_claims, my_open);
+    if (tid < num_nodes - tail)
+        bottom_up_indexed_one(tail + tid, first_parent, rev_off, rev_col, rev_et, allowed_mask,
+                              dist, cur_level, my_claims, my_open);
+    wave_add(next_count, my_claims);
+    wave_add(open_count, my_open);
+}
+
 // Rebuild a frontier from dist (nodes claimed at `level`): used when
 // dist-driven dense mode hands back to vertex-frontier mode after the
 // claim rate drops.  Claim counts are small here, so appends are cheap.
@@ -349,6 +495,33 @@ static int read_counters(unsigned int* host, const unsigned int* dev, int n, hip
     return (int)hipStreamSynchronize(s);
 }
 
+// One bottom-up level: over the parent index when the caller has one, else
+// over the reverse rows.
+static int bottom_up_level(const void* rev_off, const void* rev_col, const void* rev_et,
+                           unsigned int allowed_mask, long long num_nodes, void* dist,
+                           unsigned int cur_level, const void* first_parent,
+                           unsigned int* next_count, unsigned int* open_count, hipStream_t s) {
+    const int block = 256;
+    if (first_parent) {
+        // the 16-byte body of dist, as bfs_init lays it out
+        long long head = (long long)(((16 - ((uintptr_t)dist & 15)) & 15) / sizeof(uint32_t));
+        if (head > num_nodes) head = num_nodes;
+        const long long n4 = (num_nodes - head) / 4;
+        const int fp_vec = (((uintptr_t)first_parent + head * sizeof(uint32_t)) & 15) == 0;
+        hipLaunchKernelGGL(bfs_bottom_up_indexed_kernel, dim3(grid_for(n4, block)), dim3(block),
+                           0, s, (const uint32_t*)first_parent, (const uint64_t*)rev_off,
+                           (const uint32_t*)rev_col, (const uint8_t*)rev_et, allowed_mask,
+                           num_nodes, head, n4, fp_vec, (uint32_t*)dist, cur_level, next_count,
+                           open_count);
+    } else {
+        hipLaunchKernelGGL(bfs_bottom_up_kernel, dim3(grid_for(num_nodes, block)), dim3(block),
+                           0, s, (const uint64_t*)rev_off, (const uint32_t*)rev_col,
+                           (const uint8_t*)rev_et, allowed_mask, num_nodes, (uint32_t*)dist,
+                           cur_level, next_count, open_count);
+    }
+    return (int)hipGetLastError();
+}
+
 // One sparse level: per-vertex expansion, then the heavy queue it filled.
 static int expand_level(const void* row_off, const void* col, const void* etype,
                         unsigned int allowed_mask, const void* frontier,
@@ -414,6 +587,43 @@ extern "C" int abom_bfs_expand_edges(
     return (int)hipGetLastError();
 }
 
+// first_parent u32 [num_nodes] of (reverse CSR, allowed_mask): see
+// bfs_parent_index_kernel.  num_nodes must stay below 2^31 - 1, so that a
+// vertex id fits bits 0-30 and never reads as "none".
+extern "C" int abom_bfs_parent_index(
+    const void* rev_off, const void* rev_col, const void* rev_et, unsigned int allowed_mask,
+    long long num_nodes, void* first_parent, void* stream) {
+    if (num_nodes < 0 || num_nodes >= 0x7FFFFFFFll) return (int)hipErrorInvalidValue;
+    const int block = 256;
+    hipLaunchKernelGGL(abom::bfs_parent_index_kernel, dim3(abom::grid_for(num_nodes, block)),
+                       dim3(block), 0, (hipStream_t)stream, (const uint64_t*)rev_off,
+                       (const uint32_t*)rev_col, (const uint8_t*)rev_et, allowed_mask, num_nodes,
+                       (uint32_t*)first_parent);
+    return (int)hipGetLastError();
+}
+
+// One bottom-up pass: every unvisited vertex with a parent at cur_level gets
+// cur_level + 1; *next_count += the claims, *open_count += the vertices left
+// unvisited that have an allowed in-edge.
+extern "C" int abom_bfs_bottom_up(
+    const void* rev_off, const void* rev_col, const void* rev_et, unsigned int allowed_mask,
+    long long num_nodes, void* dist, unsigned int cur_level,
+    void* next_count, void* open_count, void* stream) {
+    return abom::bottom_up_level(rev_off, rev_col, rev_et, allowed_mask, num_nodes, dist,
+                                 cur_level, nullptr, (unsigned int*)next_count,
+                                 (unsigned int*)open_count, (hipStream_t)stream);
+}
+
+// The same pass over the parent index of (rev, allowed_mask).
+extern "C" int abom_bfs_bottom_up_indexed(
+    const void* rev_off, const void* rev_col, const void* rev_et, unsigned int allowed_mask,
+    long long num_nodes, void* dist, unsigned int cur_level, const void* first_parent,
+    void* next_count, void* open_count, void* stream) {
+    if (!first_parent) return (int)hipErrorInvalidValue;
+    return abom::bottom_up_level(rev_off, rev_col, rev_et, allowed_mask, num_nodes, dist,
+                                 cur_level, first_parent, (unsigned int*)next_count,
+                                 (unsigned int*)open_count, (hipStream_t)stream);
+}
 
 // ── C ABI: the level loop ──────────────────────────────────────────────────
 
@@ -445,12 +655,15 @@ extern "C" int abom_bfs_begin(
 // -1 to read it from the device.  ``host_counters``: pinned host u32
 // [CTR_SLOTS] for the count reads, or null to read into the stack.
 // Returns negative hip error or the number of levels run.
-extern "C" int abom_bfs_run_ex(
+// ``first_parent``: the parent index of (rev, allowed_mask) from
+// abom_bfs_parent_index, or null; with it the bottom-up levels run
+// bfs_bottom_up_indexed_kernel.
+extern "C" int abom_bfs_run_indexed(
     const void* row_off, const void* col, const void* etype, unsigned int allowed_mask,
     const void* sources, long long n_sources, void* dist, long long num_nodes,
     void* frontier_a, void* frontier_b, void* heavy_queue, void* counters,
     int max_levels, const void* edge_src, long long num_edges,
-    const void* rev_off, const void* rev_col, const void* rev_et,
+    const void* rev_off, const void* rev_col, const void* rev_et, const void* first_parent,
     int begun, long long sources_degree, void* host_counters, void* stream) {
     using namespace abom;
     hipStream_t s = (hipStream_t)stream;
@@ -492,13 +705,9 @@ extern "C" int abom_bfs_run_ex(
         if (dense) {
             stay_dense = true;
             if (bottom_up) {
-                hipLaunchKernelGGL(bfs_bottom_up_kernel,
-                                   dim3(abom::grid_for(num_nodes, 256)), dim3(256), 0, s,
-                                   (const uint64_t*)rev_off, (const uint32_t*)rev_col,
-                                   (const uint8_t*)rev_et, allowed_mask, num_nodes,
-                                   (uint32_t*)dist, (unsigned int)(level - 1), ctr + CTR_NEXT,
-                                   ctr + CTR_OPEN);
-                rc = (int)hipGetLastError();
+                rc = bottom_up_level(rev_off, rev_col, rev_et, allowed_mask, num_nodes, dist,
+                                     (unsigned int)(level - 1), first_parent, ctr + CTR_NEXT,
+                                     ctr + CTR_OPEN, s);
             } else {
                 rc = abom_bfs_expand_edges(edge_src, col, etype, allowed_mask, num_edges,
                                            row_off, dist, (unsigned int)(level - 1), nxt,
@@ -543,6 +752,21 @@ extern "C" int abom_bfs_run_ex(
         uint32_t* t = cur; cur = nxt; nxt = t;
     }
     return level;
+}
+
+// The level loop without a parent index.
+extern "C" int abom_bfs_run_ex(
+    const void* row_off, const void* col, const void* etype, unsigned int allowed_mask,
+    const void* sources, long long n_sources, void* dist, long long num_nodes,
+    void* frontier_a, void* frontier_b, void* heavy_queue, void* counters,
+    int max_levels, const void* edge_src, long long num_edges,
+    const void* rev_off, const void* rev_col, const void* rev_et,
+    int begun, long long sources_degree, void* host_counters, void* stream) {
+    return abom_bfs_run_indexed(row_off, col, etype, allowed_mask, sources, n_sources, dist,
+                                num_nodes, frontier_a, frontier_b, heavy_queue, counters,
+                                max_levels, edge_src, num_edges, rev_off, rev_col, rev_et,
+                                /*first_parent=*/nullptr, begun, sources_degree, host_counters,
+                                stream);
 }
 
 // The one-shot form of ABI v1: begin + levels, degree sum read from the device.

@@ -93,6 +93,28 @@ _SIGNATURES = {
         _c, _c, _c,           # rev_off, rev_col, rev_et
         _i32, _i64, _c, _c,   # begun, sources_degree, host_counters, stream
     ], _i32),
+    "abom_bfs_parent_index": ([
+        _c, _c, _c, _u32,  # rev_off, rev_col, rev_et, allowed_mask
+        _i64, _c, _c,      # num_nodes, first_parent, stream
+    ], _i32),
+    "abom_bfs_bottom_up": ([
+        _c, _c, _c, _u32,  # rev_off, rev_col, rev_et, allowed_mask
+        _i64, _c, _u32,    # num_nodes, dist, cur_level
+        _c, _c, _c,        # next_count, open_count, stream
+    ], _i32),
+    "abom_bfs_bottom_up_indexed": ([
+        _c, _c, _c, _u32,    # rev_off, rev_col, rev_et, allowed_mask
+        _i64, _c, _u32, _c,  # num_nodes, dist, cur_level, first_parent
+        _c, _c, _c,          # next_count, open_count, stream
+    ], _i32),
+    "abom_bfs_run_indexed": ([
+        _c, _c, _c, _u32,     # row_off, col, etype, allowed_mask
+        _c, _i64, _c, _i64,   # sources, n_sources, dist, num_nodes
+        _c, _c, _c, _c,       # frontier_a, frontier_b, heavy_queue, counters
+        _i32, _c, _i64,       # max_levels, edge_src, num_edges
+        _c, _c, _c, _c,       # rev_off, rev_col, rev_et, first_parent
+        _i32, _i64, _c, _c,   # begun, sources_degree, host_counters, stream
+    ], _i32),
     "abom_reach_hops": ([
         _c, _c, _c, _u32,        # row_off, col, etype, allowed_mask
         _c, _i32, _i32, _i64,    # sources, n_sources, words, num_nodes
@@ -790,9 +812,51 @@ def bfs_begin(row_off, sources, num_nodes: int, workspace: dict) -> None:
     _check(rc, "abom_bfs_begin")
 
 
+def bfs_parent_index(rev: dict, allowed_mask: int, num_nodes: int) -> dict:
+    """The parent index of the bottom-up pass for the reverse CSR ``rev`` and
+    ``allowed_mask``: ``first_parent`` int32 ``[num_nodes]`` (read as u32:
+    0xFFFFFFFF = no allowed in-edge, else the source of the first allowed
+    in-edge of the reverse row in bits 0-30 and bit 31 set when the row holds
+    another allowed in-edge), returned with the mask it was built for as
+    ``{"first_parent", "allowed_mask"}``.  Graph structure only: it holds for
+    as long as ``rev`` does, for every BFS with that mask.  Pass it to
+    :func:`bfs` or :func:`bfs_level_bottom_up` as ``parent_index``.
+    """
+    import torch
+
+    if num_nodes >= 2**31 - 1:
+        raise ValueError("bfs_parent_index: a vertex id must fit 31 bits "
+                         f"(num_nodes = {num_nodes})")
+    lib = load()
+    first_parent = torch.empty(num_nodes, dtype=torch.int32, device=rev["row_off"].device)
+    et = _ptr(rev["etype"]) if rev.get("etype") is not None else None
+    rc = lib.abom_bfs_parent_index(_ptr(rev["row_off"]), _ptr(rev["col"]), et, allowed_mask,
+                                   num_nodes, _ptr(first_parent), _stream())
+    _check(rc, "abom_bfs_parent_index")
+    return {"first_parent": first_parent, "allowed_mask": allowed_mask}
+
+
+def _parent_index_ptr(parent_index: Optional[dict], allowed_mask: int, num_nodes: int, what: str):
+    """Pointer to the index's words after checking that it was built for this
+    mask and this many nodes; None without an index or with the A/B toggle
+    AGENT_BOM_BFS_PARENT_INDEX=0 (bottom-up passes then walk the reverse rows)."""
+    if parent_index is None:
+        return None
+    if parent_index["allowed_mask"] != allowed_mask:
+        raise ValueError(f"{what}: parent index built for mask "
+                         f"{parent_index['allowed_mask']:#x}, called with {allowed_mask:#x}")
+    if parent_index["first_parent"].numel() != num_nodes:
+        raise ValueError(f"{what}: parent index of {parent_index['first_parent'].numel()} "
+                         f"nodes, called with {num_nodes}")
+    if os.environ.get("AGENT_BOM_BFS_PARENT_INDEX", "1") == "0":
+        return None
+    return _ptr(parent_index["first_parent"])
+
+
 def bfs(row_off, col, sources, num_nodes: int, etype=None, allowed_mask: int = 0xFFFFFFFF,
         max_levels: int = 64, workspace: Optional[dict] = None, edge_src=None,
-        rev=None, begun: bool = False, sources_degree: Optional[int] = None):
+        rev=None, begun: bool = False, sources_degree: Optional[int] = None,
+        parent_index: Optional[dict] = None):
     """Multi-source BFS over CSR; returns u32 dist (UNVISITED = 0xFFFFFFFF).
 
     ``workspace`` may carry preallocated buffers (dist/frontier_a/frontier_b/
@@ -802,6 +866,12 @@ def bfs(row_off, col, sources, num_nodes: int, etype=None, allowed_mask: int = 0
     call.  ``sources_degree``: the sum of the out-degrees of the entries of
     ``sources`` (duplicates counted), when the caller knows it; the read of
     that sum from the device and its sync are then skipped.
+    ``parent_index``: what :func:`bfs_parent_index` returned for ``rev`` and
+    ``allowed_mask``; the bottom-up levels then read one index word per
+    vertex and walk a reverse row only when its first parent is outside the
+    frontier.  An index built for another mask or node count raises
+    ``ValueError``; without ``rev`` there is no bottom-up level to use it;
+    AGENT_BOM_BFS_PARENT_INDEX=0 runs the levels without it (A/B toggle).
     """
     import torch
 
@@ -810,6 +880,7 @@ def bfs(row_off, col, sources, num_nodes: int, etype=None, allowed_mask: int = 0
     ws = workspace if workspace is not None else {}
     if begun and (workspace is None or "dist" not in workspace):
         raise ValueError("bfs: begun=True needs the workspace bfs_begin was called on")
+    first_parent_p = _parent_index_ptr(parent_index, allowed_mask, num_nodes, "bfs")
     dist, fa, fb, hq, ctr = _bfs_buffers(ws, num_nodes, dev)
     host_ctr = ws.get("host_counters")
     if host_ctr is None:
@@ -828,18 +899,55 @@ def bfs(row_off, col, sources, num_nodes: int, etype=None, allowed_mask: int = 0
         rev_off_p = _ptr(rev["row_off"])
         rev_col_p = _ptr(rev["col"])
         rev_et_p = _ptr(rev["etype"]) if rev.get("etype") is not None else None
-    rc = lib.abom_bfs_run_ex(
+    rc = lib.abom_bfs_run_indexed(
         _ptr(row_off), _ptr(col), et, allowed_mask,
         _ptr(sources), sources.numel(), _ptr(dist), num_nodes,
         _ptr(fa), _ptr(fb), _ptr(hq), _ptr(ctr), max_levels,
-        es, num_edges, rev_off_p, rev_col_p, rev_et_p,
+        es, num_edges, rev_off_p, rev_col_p, rev_et_p, first_parent_p,
         1 if begun else 0, -1 if sources_degree is None else int(sources_degree),
         _ptr(host_ctr), _stream(),
     )
     if rc < 0:
-        _check(-rc, "abom_bfs_run_ex")
+        _check(-rc, "abom_bfs_run_indexed")
     ws["levels"] = rc
     return dist[:num_nodes]
+
+
+def bfs_level_bottom_up(rev: dict, dist, cur_level: int, num_nodes: int,
+                        allowed_mask: int = 0xFFFFFFFF, parent_index: Optional[dict] = None,
+                        workspace: Optional[dict] = None):
+    """ONE bottom-up pass over the first ``num_nodes`` words of ``dist`` (in
+    place): every unvisited vertex with an allowed in-edge from a vertex at
+    ``cur_level`` gets ``cur_level + 1``.  Returns ``(claimed, open)``: the
+    vertices claimed, and the vertices left unvisited that have an allowed
+    in-edge.  With ``parent_index`` (:func:`bfs_parent_index`) the pass is the
+    indexed kernel, else the walk over the reverse rows; ``dist`` may be
+    longer than the graph and need not start on a 16-byte boundary.
+    """
+    import torch
+
+    lib = load()
+    if dist.numel() < num_nodes:
+        raise ValueError("bfs_level_bottom_up: dist is shorter than the graph")
+    first_parent_p = _parent_index_ptr(parent_index, allowed_mask, num_nodes,
+                                       "bfs_level_bottom_up")
+    ws = workspace if workspace is not None else {}
+    ctr = _buf(ws, "counters", _CTR_SLOTS, torch.int32, dist.device, zero=True)
+    ctr.zero_()
+    et = _ptr(rev["etype"]) if rev.get("etype") is not None else None
+    next_ptr, open_ptr = (ctypes.c_void_p(ctr.data_ptr() + off) for off in (_CTR_NEXT, _CTR_OPEN))
+    if first_parent_p is not None:
+        rc = lib.abom_bfs_bottom_up_indexed(
+            _ptr(rev["row_off"]), _ptr(rev["col"]), et, allowed_mask, num_nodes, _ptr(dist),
+            cur_level, first_parent_p, next_ptr, open_ptr, _stream())
+        _check(rc, "abom_bfs_bottom_up_indexed")
+    else:
+        rc = lib.abom_bfs_bottom_up(
+            _ptr(rev["row_off"]), _ptr(rev["col"]), et, allowed_mask, num_nodes, _ptr(dist),
+            cur_level, next_ptr, open_ptr, _stream())
+        _check(rc, "abom_bfs_bottom_up")
+    counts = ctr.cpu()
+    return int(counts[_CTR_NEXT // 4]), int(counts[_CTR_OPEN // 4])
 
 
 def bfs_level(row_off, col, frontier, dist, level: int, etype=None,
