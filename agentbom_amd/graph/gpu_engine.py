@@ -50,6 +50,15 @@ construction) and stays resident in HBM3E.  On top of it:
                          (``build_agent_index``) by the two kernels of
                          ops/csrc/blast_hops.hip; packages that overflow an
                          LDS cap are recomputed by an exact join
+- ``remediation_plan()`` the fix-first plan: findings grouped per (name,
+                         version) item with their counts, worst severity, KEV,
+                         largest fixed version and the distinct servers,
+                         agents, creds and tools over every install, ranked;
+                         folded and unioned by the kernels of
+                         ops/csrc/remediation.hip (LDS sets per wave, a
+                         bitmap pool for the zipf heads;
+                         AGENT_BOM_REMEDIATION_NATIVE=0 runs an exact torch
+                         join instead)
 - ``blast_radius_query()`` batched bounded BFS for p50 query latency /
                          the /v1/graph read path
 - ``pagerank()`` / ``betweenness()`` / ``choke_points()`` centrality on
@@ -567,6 +576,10 @@ class EstateEngine:
         self._hop_factor = torch.tensor(
             [0.0] + [HOP_RISK_FACTORS[h] for h in range(1, 6)],
             dtype=torch.float32, device=dev)
+        # remediation plan: package -> (name, version) item, built at first
+        # use, and the workspace of ops/csrc/remediation.hip
+        self._remed_items = None
+        self._remed_ws: dict = {}
 
     def _build_csr(self, src, dst, et):
         """GPU CSR construction: stable sort by src, bincount offsets."""
@@ -1061,6 +1074,86 @@ class EstateEngine:
         pkg_nodes = (step_res["pkg_idx"] + self.estate.pkg_base).to(torch.int64)
         # pkg_idx arrives sorted: no re-sort needed
         return self._blast_hops(torch.unique_consecutive(pkg_nodes), None, max_depth)
+
+    def remediation_items(self):
+        """(item_of int32 [P], number of items): the index of every package's
+        (pkg_group_key, pkg_key_hi, pkg_key_lo) triple among the distinct
+        triples in ascending unsigned lexicographic order.  Built with torch
+        at first use from the package columns alone, so it is the same with
+        and without a dedup layout, and cached."""
+        if self._remed_items is None:
+            torch = self.torch
+            P = self.pkg_group_key.numel()
+            # stable sorts from the least significant column up; the sign
+            # flip turns the int64 order into the u64 order
+            order = torch.arange(P, device=self.device)
+            for col in (self.pkg_key_lo, self.pkg_key_hi, self.pkg_group_key):
+                order = order[torch.argsort((col ^ _SIGN64)[order], stable=True)]
+            g, h, l = (c[order] for c in (self.pkg_group_key, self.pkg_key_hi, self.pkg_key_lo))
+            new = torch.ones(P, dtype=torch.bool, device=self.device)
+            new[1:] = (g[1:] != g[:-1]) | (h[1:] != h[:-1]) | (l[1:] != l[:-1])
+            rank = torch.cumsum(new.to(torch.int32), 0, dtype=torch.int32) - 1
+            item_of = torch.empty(P, dtype=torch.int32, device=self.device)
+            item_of[order] = rank
+            self._remed_items = (item_of, int(rank[-1]) + 1 if P else 0)
+        return self._remed_items
+
+    def remediation_plan(self, step_res=None, k: Optional[int] = 100) -> dict:
+        """Fix-first remediation plan: the findings of a step grouped per
+        (name, version) item -- "upgrade this and you clear that".
+
+        Returns tensors on the engine's device, one entry per matched item,
+        the first ``k`` (all with ``k=None``) in the order max_score
+        descending, n_agents descending, item index ascending: the keys of
+        ``cpu_ref.REMEDIATION_KEYS`` (semantics: ``cpu_ref.remediation_plan``)
+        and ``agents_pct`` fp32 = 100 * n_agents / estate.n_agents; plus
+        ``n_items``, the number of matched items.  On the GPU the per-item
+        arrays come from the kernels of ops/csrc/remediation.hip
+        (AGENT_BOM_REMEDIATION_NATIVE=0: from an exact torch join), on the
+        CPU from the oracle.  Calls :meth:`step` when ``step_res`` is None."""
+        torch = self.torch
+        if step_res is None:
+            step_res = self.step()
+        item_of, n_items = self.remediation_items()
+        pkg_idx, win_idx, scores = step_res["pkg_idx"], step_res["win_idx"], step_res["scores"]
+        if self.use_gpu:
+            from agentbom_amd.ops import native
+
+            pkg_idx, win_idx = pkg_idx.contiguous(), win_idx.contiguous()
+            scores = scores.contiguous()
+            if native.remediation_native_enabled():
+                per = native.remediation_items(
+                    pkg_idx, win_idx, scores, item_of, n_items, self.arena, self.rev,
+                    self.reach_index, ET_CONTAINS, self.estate.pkg_base, self._remed_ws)
+            else:
+                per = native.remediation_items_join(
+                    pkg_idx, win_idx, scores, item_of, self.arena, self.rev,
+                    self.reach_index, ET_CONTAINS, self.estate.pkg_base)
+            pct = per["n_agents"].to(torch.float32) * 100.0 / float(self.estate.n_agents)
+            # stable sorts from the last key up; positions are in item order
+            order = torch.argsort(per["n_agents"], descending=True, stable=True)
+            order = order[torch.argsort(per["max_score"][order], descending=True, stable=True)]
+        else:
+            from agentbom_amd.ops import cpu_ref
+
+            windows = self.arena["windows"]
+            ref = cpu_ref.remediation_plan(
+                pkg_idx.numpy(), win_idx.numpy(), scores.numpy(), item_of.numpy(),
+                self.rev["row_off"].numpy(), self.rev["col"].numpy(), self.rev["etype"].numpy(),
+                self.fwd["row_off"].numpy(), self.fwd["col"].numpy(), self.fwd["etype"].numpy(),
+                ET_CONTAINS, ET_USES, ET_HAS_CRED, ET_PROVIDES_TOOL, self.estate.pkg_base,
+                windows["flags"].numpy(), windows["fixed_hi"].numpy(),
+                windows["fixed_lo"].numpy(), self.arena["severity"].numpy(),
+                self.arena["kev"].numpy(), self.estate.n_agents)
+            per = {key: torch.from_numpy(ref[key]) for key in cpu_ref.REMEDIATION_KEYS}
+            pct, order = torch.from_numpy(ref["agents_pct"]), torch.from_numpy(ref["order"])
+        n_matched = order.numel()
+        if k is not None:
+            order = order[:max(int(k), 0)]
+        plan = {key: value[order] for key, value in per.items()}
+        plan["agents_pct"] = pct[order]
+        plan["n_items"] = n_matched
+        return plan
 
     def _score_cpu(self, counts, pos, pkg_nodes, win_idx, dist):
         """CPU oracle of the fused score_gather kernel: (scores, n_agents,

@@ -506,3 +506,88 @@ def blast_hops(pkgs, rev_off, rev_col, rev_et, et_contains, et_uses, et_has_cred
                 seen_s |= frontier
         t_creds[i] = len(union(cr, union(srv, transitive)))
     return hop_agents, t_creds, hop_depth
+
+
+# the per-item arrays of the remediation plan, in the order they are documented
+REMEDIATION_KEYS = (
+    "item", "rep_pkg", "installs", "n_findings", "n_vulns", "max_score", "worst_sev", "kev",
+    "fix_hi", "fix_lo", "n_unfixed", "n_servers", "n_agents", "n_creds", "n_tools")
+
+
+def remediation_item_of(pkg_group_key, pkg_key_hi, pkg_key_lo):
+    """``item_of`` int32 [P]: the index of every package's (group key, key hi,
+    key lo) triple among the distinct triples in ascending unsigned
+    lexicographic order."""
+    triples = list(zip(np.asarray(pkg_group_key).view(np.uint64).tolist(),
+                       np.asarray(pkg_key_hi).view(np.uint64).tolist(),
+                       np.asarray(pkg_key_lo).view(np.uint64).tolist()))
+    rank = {t: i for i, t in enumerate(sorted(set(triples)))}
+    return np.asarray([rank[t] for t in triples], dtype=np.int32)
+
+
+def remediation_plan(pkg_idx, win_idx, scores, item_of,
+                     rev_off, rev_col, rev_et, fwd_off, fwd_col, fwd_et,
+                     et_contains: int, et_uses: int, et_has_cred: int, et_tool: int,
+                     pkg_base: int, w_flags, w_fixed_hi, w_fixed_lo, a_severity, a_kev,
+                     n_agents_total: int) -> dict:
+    """Fix-first remediation plan of a step's findings, from the definitions.
+
+    An item is a distinct (name, version); ``item_of`` maps a package index to
+    its item.  Per item with at least one finding, in ascending item index
+    (the keys of ``REMEDIATION_KEYS``): ``rep_pkg`` its smallest matched
+    package, ``installs`` its distinct matched packages, ``n_findings``,
+    ``n_vulns`` distinct windows, ``max_score`` fp32, ``worst_sev`` and ``kev``
+    uint8 over its windows, (``fix_hi``, ``fix_lo``) int64 bit patterns of the
+    largest fixed key -- unsigned 128-bit order -- over its windows with
+    WF_HAS_FIXED (0, 0 without one), ``n_unfixed`` distinct windows without
+    it, ``n_servers`` distinct sources of CONTAINS edges into a matched
+    install and ``n_agents`` / ``n_creds`` / ``n_tools`` the distinct agents
+    (USES sources), creds (HAS_CRED targets) and tools (PROVIDES_TOOL targets)
+    of those servers, unfiltered.  On top: ``agents_pct`` fp32 = (100 *
+    n_agents) / n_agents_total and ``order`` int64, the positions sorted by
+    max_score descending, n_agents descending, item ascending."""
+    pkg_idx = np.asarray(pkg_idx, dtype=np.int64)
+    win_idx = np.asarray(win_idx, dtype=np.int64)
+    scores = np.asarray(scores, dtype=np.float32)
+    fhi, flo = np.asarray(w_fixed_hi).view(np.uint64), np.asarray(w_fixed_lo).view(np.uint64)
+
+    def row(off, col, et, node, want):
+        return {int(col[e]) for e in range(int(off[node]), int(off[node + 1])) if et[e] == want}
+
+    groups: dict = {}
+    for f in range(len(pkg_idx)):
+        groups.setdefault(int(item_of[pkg_idx[f]]), []).append(f)
+    out = {k: [] for k in REMEDIATION_KEYS}
+    for item in sorted(groups):
+        fs = groups[item]
+        pkgs = {int(pkg_idx[f]) for f in fs}
+        wins = {int(win_idx[f]) for f in fs}
+        fixed = [(int(fhi[w]), int(flo[w])) for w in wins if w_flags[w] & WF_HAS_FIXED]
+        best = max(fixed) if fixed else (0, 0)
+        servers: set = set()
+        for p in pkgs:
+            servers |= row(rev_off, rev_col, rev_et, p + pkg_base, et_contains)
+        agents, creds, tools = set(), set(), set()
+        for s in servers:
+            agents |= row(rev_off, rev_col, rev_et, s, et_uses)
+            creds |= row(fwd_off, fwd_col, fwd_et, s, et_has_cred)
+            tools |= row(fwd_off, fwd_col, fwd_et, s, et_tool)
+        for key, value in zip(REMEDIATION_KEYS, (
+                item, min(pkgs), len(pkgs), len(fs), len(wins),
+                max(scores[f] for f in fs), max(int(a_severity[w]) for w in wins),
+                int(any(a_kev[w] for w in wins)), best[0], best[1],
+                len(wins) - len(fixed), len(servers), len(agents), len(creds), len(tools))):
+            out[key].append(value)
+    dtypes = dict.fromkeys(REMEDIATION_KEYS, np.int32)
+    dtypes.update(max_score=np.float32, worst_sev=np.uint8, kev=np.uint8)
+    res = {k: np.asarray(out[k], dtype=dtypes[k]) for k in REMEDIATION_KEYS
+           if k not in ("fix_hi", "fix_lo")}
+    for k in ("fix_hi", "fix_lo"):
+        res[k] = np.asarray(out[k], dtype=np.uint64).view(np.int64)
+    res["agents_pct"] = (np.float32(100.0) * res["n_agents"].astype(np.float32)
+                         / np.float32(n_agents_total))
+    M = len(res["item"])
+    res["order"] = np.asarray(
+        sorted(range(M), key=lambda m: (-float(res["max_score"][m]), -int(res["n_agents"][m]),
+                                        int(res["item"][m]))), dtype=np.int64)
+    return res

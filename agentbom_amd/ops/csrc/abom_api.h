@@ -198,6 +198,42 @@ int abom_blast_hops_sized(
     void* queue, void* counters, void* host_counters,
     void* out_hop_agents, void* out_creds, void* out_depth, void* out_overflow, void* stream);
 
+// remediation.hip (the remediation plan per (name, version) item, four calls
+// on one stream: state is u32 [items, 8], pool u32 [pool_slices *
+// ((num_rows + 31) / 32 + 3 * ((node_span + 31) / 32))], counters u32 [4] =
+// {matched items, tier-2 items, pool rounds, matched installs}, all three
+// all-zero on entry and after abom_remediation_union; host_counters is pinned
+// host u32 [4], written by the fold and again by the union.  pkg_idx and
+// win_idx are int64 [num_findings], pkg_idx ascending; items is the sorted
+// `matched` list, items_off the exclusive prefix of out_installs with the
+// total at [num_items].  abom_remediation_cap returns a cap of the wave
+// kernel, not a hipError_t: 0 = servers, 1 = agents, 2 = creds, 3 = tools,
+// 4 = the install count above which an item skips the wave kernel, else -1)
+int abom_remediation_cap(int which);
+int abom_remediation_fold(
+    const void* pkg_idx, const void* win_idx, const void* scores, long long num_findings,
+    const void* item_of, const void* a_severity, const void* a_kev,
+    void* state, void* matched, void* counters, void* host_counters, void* stream);
+int abom_remediation_gather(
+    const void* items, long long num_items,
+    const void* pkg_idx, const void* win_idx, long long num_findings,
+    const void* w_flags, const void* w_fixed_hi, const void* w_fixed_lo, void* state,
+    void* out_rep_pkg, void* out_installs, void* out_findings, void* out_vulns,
+    void* out_score, void* out_sev, void* out_kev, void* out_fix_hi, void* out_fix_lo,
+    void* out_unfixed, void* stream);
+int abom_remediation_scatter(
+    const void* pkg_idx, long long num_findings, const void* item_of, void* state,
+    const void* items_off, long long num_items, long long num_installs, void* csr_pkgs,
+    void* stream);
+int abom_remediation_union(
+    const void* items, long long num_items, const void* items_off, const void* csr_pkgs,
+    long long pkg_base,
+    const void* rev_off, const void* rev_col, const void* rev_et, int et_contains,
+    const void* reach_off, const void* reach_col, long long row_base, long long num_rows,
+    long long node_span, void* state, void* queue, void* pool, long long pool_slices,
+    void* counters, void* host_counters,
+    void* out_servers, void* out_agents, void* out_creds, void* out_tools, void* stream);
+
 // paths.hip (edge_weight and node_gate are nullable)
 int abom_path_relax(
     const void* edge_src, const void* col, const void* etype, const void* edge_weight,

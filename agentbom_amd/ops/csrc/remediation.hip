@@ -1,0 +1,518 @@
+// Fix-first remediation plan on gfx950: the findings of a step folded per
+// (name, version) item, and per matched item the distinct servers that hold
+// an install and the distinct union of their agents, creds and tools.
+// Semantics: cpu_ref.remediation_plan.  Every output is a count, a max of
+// integers or an index, so no order of lanes, waves or atomics can show.
+//
+// Four entry points, enqueued in this order on one stream:
+//
+// abom_remediation_fold     one thread per finding into `state`, u32 [I, 8],
+//   one 32-byte row per item: {findings, installs, score bits, severity, kev,
+//   F - first head finding, slot, cursor}.  Lanes next to each other that hold
+//   the same item (the findings of one package are a run) are combined in the
+//   wave first; the run's first lane does the atomics.  The wave that finds
+//   `findings` at 0 appends the item to `matched`.  counters = {matched
+//   items, tier-2 items, pool rounds, matched installs}, copied to pinned
+//   host memory: the caller reads them once, sorts `matched` and sizes the
+//   outputs.
+// abom_remediation_gather   one wave per matched item, ascending: the folded
+//   fields move to the outputs and their words of `state` return to 0; the
+//   wave then walks the finding run of the item's first package for the
+//   distinct windows, the unfixed ones and the largest fixed key.  slot =
+//   position + 1 stays for the scatter.
+// abom_remediation_scatter  one thread per finding; the head of a package run
+//   claims a place in its item's span of `csr_pkgs` through the cursor.
+// abom_remediation_union    tier 1, one wave per matched item: distinct
+//   servers, agents, creds and tools as capped LDS sets (abom_sets.h).  An
+//   item past a cap, or with more than REMED_T1_INSTALLS installs, goes to
+//   the tier-2 queue.  Tier 2, one block per slice of the bitmap pool: a
+//   slice holds one bit per reach-index row and three planes of one bit per
+//   node id below `node_span`; atomicOr sets a bit and the old word says
+//   whether it was new.  A block walks its item twice, the second time
+//   clearing what the first set, so a slice is all-zero whenever a block
+//   leaves an item, and block b takes the queued items b, b + slices, ...
+//   Tier 1 also returns slot and cursor to 0: `state`, `pool` and `counters`
+//   are all-zero on return.
+//
+// Preconditions, as EstateEngine.step and build_reach_index give them:
+// pkg_idx ascending; the installs of one item carry the same windows; every
+// source of a CONTAINS edge has a reach-index row; fewer than 2^31 findings.
+//
+// CDNA4 notes: tier 1 runs 4 waves per block; LDS per wave = the four caps
+// (256 + 256 + 256 + 512 words), a 64-word candidate stage and two 64-word
+// segment tables = 1472 words = 5.75 KiB -> 23 KiB per block -> 6 blocks per
+// CU fit the 160 KiB LDS (24 of 32 wave slots).  Tier 2 holds a 1024-entry
+// server list, 4 KiB per block.
+
+#include "abom_api.h"
+#include "abom_sets.h"
+
+namespace abom {
+
+constexpr int REMED_SRV_CAP = 256;
+constexpr int REMED_AG_CAP = 256;
+constexpr int REMED_CR_CAP = 256;
+constexpr int REMED_TL_CAP = 512;
+constexpr int REMED_WAVES = 4;
+// an item with more installs than this skips tier 1: on an estate that
+// spreads installs over its servers it would pass the server cap anyway
+constexpr int REMED_T1_INSTALLS = 4 * REMED_SRV_CAP;
+constexpr int REMED_T2_LIST = 1024;
+constexpr int REMED_ROW = 8;  // u32 words per item of `state`
+
+enum RemedWord { RW_FINDINGS, RW_INSTALLS, RW_SCORE, RW_SEV, RW_KEV, RW_HEAD, RW_SLOT, RW_CURSOR };
+enum RemedCounter { RC_MATCHED, RC_QUEUED, RC_ROUNDS, RC_INSTALLS };
+
+__global__ void __launch_bounds__(256) remed_fold_kernel(
+    const long long* __restrict__ pkg_idx, const long long* __restrict__ win_idx,
+    const uint32_t* __restrict__ score_bits, long long F,
+    const int* __restrict__ item_of, const uint8_t* __restrict__ a_sev,
+    const uint8_t* __restrict__ a_kev,
+    uint32_t* __restrict__ state, uint32_t* __restrict__ matched,
+    unsigned int* __restrict__ counters) {
+    const int lane = threadIdx.x & 63;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const long long start = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    // wave-uniform trip count: every lane reaches the ballots and shuffles
+    for (long long base = start - lane; base < F; base += stride) {
+        const long long f = base + lane;
+        const bool active = f < F;
+        long long pkg = -1;
+        bool head = false;
+        uint32_t item = 0xFFFFFFFFu, bits = 0, sevkev = 0;
+        if (active) {
+            pkg = pkg_idx[f];
+            head = f == 0 || pkg_idx[f - 1] != pkg;
+            item = (uint32_t)item_of[pkg];
+            const long long w = win_idx[f];
+            // scores are >= 0: the order of the bit patterns is the order of the values
+            bits = score_bits[f];
+            sevkev = (uint32_t)a_sev[w] | (a_kev[w] ? 0x100u : 0u);
+        }
+        // runs of neighbouring lanes with one item: [lane, end) for a run's first lane
+        const uint32_t left = __shfl_up(item, 1, 64);
+        const bool first = active && (lane == 0 || left != item);
+        const unsigned long long firsts = __ballot(first);
+        const unsigned long long heads = __ballot(head);
+        const int n_active = __popcll(__ballot(active));  // the active lanes are a prefix
+        const unsigned long long above = firsts & ~((2ull << lane) - 1);
+        const int end = above ? __ffsll((long long)above) - 1 : n_active;
+        uint32_t mx = bits, sv = sevkev & 0xFFu, kv = sevkev >> 8;
+        for (int k = 1; __ballot(first && lane + k < end); ++k) {
+            const uint32_t b2 = __shfl_down(bits, k, 64);
+            const uint32_t s2 = __shfl_down(sevkev, k, 64);
+            if (first && lane + k < end) {
+                mx = b2 > mx ? b2 : mx;
+                sv = (s2 & 0xFFu) > sv ? (s2 & 0xFFu) : sv;
+                kv |= s2 >> 8;
+            }
+        }
+        bool fresh = false;
+        if (first) {
+            uint32_t* row = state + (size_t)item * REMED_ROW;
+            const unsigned long long below_end = end >= 64 ? ~0ull : (1ull << end) - 1;
+            const unsigned long long run_heads = heads & below_end & ~((1ull << lane) - 1);
+            fresh = atomicAdd(&row[RW_FINDINGS], (uint32_t)(end - lane)) == 0;
+            if (run_heads) {
+                // pkg_idx ascends: the first head of the run is its smallest package
+                const long long f_head = base + __ffsll((long long)run_heads) - 1;
+                atomicAdd(&row[RW_INSTALLS], (uint32_t)__popcll(run_heads));
+                atomicMax(&row[RW_HEAD], (uint32_t)(F - f_head));
+            }
+            if (mx) atomicMax(&row[RW_SCORE], mx);
+            if (sv) atomicMax(&row[RW_SEV], sv);
+            if (kv) atomicOr(&row[RW_KEV], 1u);
+        }
+        wave_queue_push(fresh, item, matched, &counters[RC_MATCHED], lane);
+        wave_count_flag(head, &counters[RC_INSTALLS], lane);
+    }
+}
+
+__global__ void __launch_bounds__(256) remed_gather_kernel(
+    const int* __restrict__ items, long long M,
+    const long long* __restrict__ pkg_idx, const long long* __restrict__ win_idx, long long F,
+    const uint8_t* __restrict__ w_flags, const long long* __restrict__ w_fixed_hi,
+    const long long* __restrict__ w_fixed_lo, uint32_t* __restrict__ state,
+    int* __restrict__ out_rep_pkg, int* __restrict__ out_installs, int* __restrict__ out_findings,
+    int* __restrict__ out_vulns, uint32_t* __restrict__ out_score, uint8_t* __restrict__ out_sev,
+    uint8_t* __restrict__ out_kev, long long* __restrict__ out_fix_hi,
+    long long* __restrict__ out_fix_lo, int* __restrict__ out_unfixed) {
+    const WaveId w = wave_id(REMED_WAVES);
+    const int lane = w.lane;
+    for (long long m = w.wave; m < M; m += w.n_waves) {
+        uint32_t* row = state + (size_t)items[m] * REMED_ROW;
+        const uint32_t n_find = row[RW_FINDINGS], n_inst = row[RW_INSTALLS];
+        const uint32_t score = row[RW_SCORE], sev = row[RW_SEV], kev = row[RW_KEV];
+        // a matched item has a head finding, so 1 <= row[RW_HEAD] <= F
+        long long head = F - (long long)row[RW_HEAD];
+        if (head >= F) head = F - 1;
+        const long long rep = pkg_idx[head];
+        // the finding run of the first package: distinct windows, the unfixed
+        // ones, and the largest fixed key as unsigned 128 bits
+        int n_vulns = 0, n_unfixed = 0;
+        uint64_t fhi = 0, flo = 0;
+        for (long long base = head;; base += 64) {
+            const long long f = base + lane;
+            const bool in = f < F && pkg_idx[f] == rep;
+            if (in) {
+                const long long win = win_idx[f];
+                bool dup = false;
+                for (long long g = head; g < f; ++g) dup |= win_idx[g] == win;
+                if (!dup) {
+                    ++n_vulns;
+                    if (w_flags[win] & WF_HAS_FIXED) {
+                        const uint64_t hi = (uint64_t)w_fixed_hi[win], lo = (uint64_t)w_fixed_lo[win];
+                        if (key_gt(hi, lo, fhi, flo)) { fhi = hi; flo = lo; }
+                    } else {
+                        ++n_unfixed;
+                    }
+                }
+            }
+            if (__ballot(in) != ~0ull) break;
+        }
+        n_vulns = wave_sum(n_vulns);
+        n_unfixed = wave_sum(n_unfixed);
+        for (int off = 32; off > 0; off >>= 1) {
+            const uint64_t hi = (uint64_t)__shfl_down((long long)fhi, off, 64);
+            const uint64_t lo = (uint64_t)__shfl_down((long long)flo, off, 64);
+            if (key_gt(hi, lo, fhi, flo)) { fhi = hi; flo = lo; }
+        }
+        if (lane == 0) {
+            out_rep_pkg[m] = (int)rep;
+            out_installs[m] = (int)n_inst;
+            out_findings[m] = (int)n_find;
+            out_vulns[m] = n_vulns;
+            out_score[m] = score;
+            out_sev[m] = (uint8_t)sev;
+            out_kev[m] = (uint8_t)kev;
+            out_fix_hi[m] = (long long)fhi;
+            out_fix_lo[m] = (long long)flo;
+            out_unfixed[m] = n_unfixed;
+            row[RW_FINDINGS] = 0; row[RW_INSTALLS] = 0; row[RW_SCORE] = 0;
+            row[RW_SEV] = 0; row[RW_KEV] = 0; row[RW_HEAD] = 0;
+            row[RW_SLOT] = (uint32_t)m + 1;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) remed_scatter_kernel(
+    const long long* __restrict__ pkg_idx, long long F, const int* __restrict__ item_of,
+    uint32_t* __restrict__ state, const int* __restrict__ items_off, long long M,
+    long long n_installs, int* __restrict__ csr_pkgs) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += stride) {
+        const long long pkg = pkg_idx[f];
+        if (f != 0 && pkg_idx[f - 1] == pkg) continue;
+        uint32_t* row = state + (size_t)(uint32_t)item_of[pkg] * REMED_ROW;
+        const long long m = (long long)row[RW_SLOT] - 1;
+        if (m < 0 || m >= M) continue;  // not reached with the gather's slots
+        const long long at = (long long)items_off[m] + atomicAdd(&row[RW_CURSOR], 1u);
+        if (at < n_installs) csr_pkgs[at] = (int)pkg;
+    }
+}
+
+struct RemedGraph {
+    const uint64_t* rev_off;
+    const uint32_t* rev_col;
+    const uint8_t* rev_et;
+    uint8_t et_contains;
+    long long pkg_base;
+    const int* items_off;   // [M + 1]
+    const int* csr_pkgs;    // package indices, grouped by matched item
+};
+
+// Tier 1: one wave per matched item.
+__global__ void __launch_bounds__(256) remed_union_wave_kernel(
+    const int* __restrict__ items, long long M, RemedGraph g, HopIndex ix,
+    uint32_t* __restrict__ state, uint32_t* __restrict__ queue,
+    unsigned int* __restrict__ counters,
+    int* __restrict__ out_servers, int* __restrict__ out_agents, int* __restrict__ out_creds,
+    int* __restrict__ out_tools) {
+    __shared__ uint32_t lds_srv[REMED_WAVES][REMED_SRV_CAP];
+    __shared__ uint32_t lds_ag[REMED_WAVES][REMED_AG_CAP];
+    __shared__ uint32_t lds_cr[REMED_WAVES][REMED_CR_CAP];
+    __shared__ uint32_t lds_tl[REMED_WAVES][REMED_TL_CAP];
+    __shared__ uint32_t lds_stage[REMED_WAVES][64];
+    __shared__ int lds_beg[REMED_WAVES][64];
+    __shared__ int lds_pref[REMED_WAVES][64];
+
+    const WaveId w = wave_id(REMED_WAVES);
+    const int lane = w.lane, wid = w.wid;
+    uint32_t* srv = lds_srv[wid];
+    uint32_t* stage = lds_stage[wid];
+    int* t_beg = lds_beg[wid];
+    int* t_pref = lds_pref[wid];
+
+    for (long long m = w.wave; m < M; m += w.n_waves) {
+        if (lane == 0) {
+            uint32_t* row = state + (size_t)items[m] * REMED_ROW;
+            row[RW_SLOT] = 0;
+            row[RW_CURSOR] = 0;
+        }
+        const int beg = g.items_off[m];
+        const int n_inst = g.items_off[m + 1] - beg;
+        int n_srv = 0, n_ag = 0, n_cr = 0, n_tl = 0;
+        bool ok = n_inst <= REMED_T1_INSTALLS;
+        // the distinct sources of CONTAINS edges into the installs, one
+        // install per lane, the k-th edge of every lane's reverse row at a time
+        for (int base = 0; base < n_inst && ok; base += 64) {
+            uint64_t e = 0, e_end = 0;
+            if (base + lane < n_inst) {
+                const long long node = g.pkg_base + g.csr_pkgs[beg + base + lane];
+                e = g.rev_off[node];
+                e_end = g.rev_off[node + 1];
+            }
+            for (; ok && __ballot(e < e_end); ++e) {
+                const bool valid = e < e_end && g.rev_et[e] == g.et_contains;
+                const uint32_t v = valid ? g.rev_col[e] : 0u;
+                ok = append_distinct(srv, n_srv, REMED_SRV_CAP, v, valid, stage, lane);
+            }
+        }
+        ok = ok && expand_append<AGENTS_OF_SERVER>(ix, srv, 0, n_srv, lds_ag[wid], n_ag,
+                                                  REMED_AG_CAP, t_beg, t_pref, stage, lane);
+        ok = ok && expand_append<CREDS_OF_SERVER>(ix, srv, 0, n_srv, lds_cr[wid], n_cr,
+                                                 REMED_CR_CAP, t_beg, t_pref, stage, lane);
+        ok = ok && expand_append<TOOLS_OF_SERVER>(ix, srv, 0, n_srv, lds_tl[wid], n_tl,
+                                                 REMED_TL_CAP, t_beg, t_pref, stage, lane);
+        if (ok && lane == 0) {
+            out_servers[m] = n_srv;
+            out_agents[m] = n_ag;
+            out_creds[m] = n_cr;
+            out_tools[m] = n_tl;
+        }
+        wave_queue_push(!ok && lane == 0, (uint32_t)m, queue, &counters[RC_QUEUED], lane);
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+struct RemedSlice {
+    uint32_t* srv;        // one bit per reach-index row
+    uint32_t* planes;     // agents, creds, tools: plane_words each, one bit per node id
+    long long plane_words;
+    uint32_t node_span;
+};
+
+// The index row `r`, entries start, start + step, ...: set and count new bits
+// (CLEAR = false) or return their words to zero.
+template <bool CLEAR>
+__device__ __forceinline__ void visit_row(const HopIndex& ix, const RemedSlice& sl, uint32_t r,
+                                          int start, int step, int3& fresh) {
+    const int4 off = ix.reach_off[r];
+    for (int t = off.x + start; t < off.w; t += step) {
+        const uint32_t v = ix.reach_col[t];
+        if (v >= sl.node_span) continue;  // not reached: node_span covers reach_col
+        const int kind = t < off.y ? 0 : t < off.z ? 1 : 2;
+        uint32_t* word = sl.planes + kind * sl.plane_words + (v >> 5);
+        if (CLEAR) {
+            *word = 0;
+        } else if (!(atomicOr(word, 1u << (v & 31)) & (1u << (v & 31)))) {
+            fresh.x += kind == 0;
+            fresh.y += kind == 1;
+            fresh.z += kind == 2;
+        }
+    }
+}
+
+// One walk of item m by the block: per chunk of 256 installs, a thread marks
+// the servers of its install, the servers whose bit changed go to an LDS
+// list, and the waves then visit the listed servers' index rows.
+template <bool CLEAR>
+__device__ __forceinline__ void walk_item(const RemedGraph& g, const HopIndex& ix,
+                                          const RemedSlice& sl, int beg, int n_inst,
+                                          uint32_t* list, unsigned* n_list, int& n_srv,
+                                          int3& fresh) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    for (int base = 0; base < n_inst; base += 256) {
+        if (threadIdx.x == 0) *n_list = 0;
+        __syncthreads();
+        if (base + (int)threadIdx.x < n_inst) {
+            const long long node = g.pkg_base + g.csr_pkgs[beg + base + threadIdx.x];
+            for (uint64_t e = g.rev_off[node]; e < g.rev_off[node + 1]; ++e) {
+                if (g.rev_et[e] != g.et_contains) continue;
+                const uint32_t r = g.rev_col[e] - ix.row_base;
+                if (r >= ix.num_rows) continue;  // not reached: see the preconditions
+                const uint32_t bit = 1u << (r & 31);
+                const uint32_t old = CLEAR ? atomicAnd(sl.srv + (r >> 5), ~bit)
+                                           : atomicOr(sl.srv + (r >> 5), bit);
+                if (((old & bit) != 0) != CLEAR) continue;  // another install had it
+                ++n_srv;
+                const unsigned slot = atomicAdd(n_list, 1u);
+                if (slot < REMED_T2_LIST) list[slot] = r;
+                else visit_row<CLEAR>(ix, sl, r, 0, 1, fresh);  // list full: alone
+            }
+        }
+        __syncthreads();
+        const unsigned n = *n_list < REMED_T2_LIST ? *n_list : REMED_T2_LIST;
+        for (unsigned j = wid; j < n; j += REMED_WAVES) visit_row<CLEAR>(ix, sl, list[j], lane, 64, fresh);
+        __syncthreads();
+    }
+}
+
+// Tier 2: block b owns slice b of the pool and takes the queued items b,
+// b + gridDim.x, ...
+__global__ void __launch_bounds__(256) remed_union_block_kernel(
+    RemedGraph g, HopIndex ix, const uint32_t* __restrict__ queue,
+    unsigned int* __restrict__ counters, uint32_t* __restrict__ pool,
+    long long srv_words, long long plane_words, uint32_t node_span,
+    int* __restrict__ out_servers, int* __restrict__ out_agents, int* __restrict__ out_creds,
+    int* __restrict__ out_tools) {
+    __shared__ uint32_t list[REMED_T2_LIST];
+    __shared__ unsigned n_list;
+    __shared__ int totals[4];
+    const unsigned n_queued = counters[RC_QUEUED];
+    RemedSlice sl;
+    sl.srv = pool + (size_t)blockIdx.x * (size_t)(srv_words + 3 * plane_words);
+    sl.planes = sl.srv + srv_words;
+    sl.plane_words = plane_words;
+    sl.node_span = node_span;
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        counters[RC_ROUNDS] = (n_queued + gridDim.x - 1) / gridDim.x;
+    for (unsigned q = blockIdx.x; q < n_queued; q += gridDim.x) {
+        const long long m = queue[q];
+        const int beg = g.items_off[m];
+        const int n_inst = g.items_off[m + 1] - beg;
+        if (threadIdx.x < 4) totals[threadIdx.x] = 0;
+        int n_srv = 0, unused_srv = 0;
+        int3 fresh = make_int3(0, 0, 0), unused = make_int3(0, 0, 0);
+        walk_item<false>(g, ix, sl, beg, n_inst, list, &n_list, n_srv, fresh);
+        walk_item<true>(g, ix, sl, beg, n_inst, list, &n_list, unused_srv, unused);
+        n_srv = wave_sum(n_srv);
+        fresh.x = wave_sum(fresh.x);
+        fresh.y = wave_sum(fresh.y);
+        fresh.z = wave_sum(fresh.z);
+        if ((threadIdx.x & 63) == 0) {
+            atomicAdd(&totals[0], n_srv);
+            atomicAdd(&totals[1], fresh.x);
+            atomicAdd(&totals[2], fresh.y);
+            atomicAdd(&totals[3], fresh.z);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            out_servers[m] = totals[0];
+            out_agents[m] = totals[1];
+            out_creds[m] = totals[2];
+            out_tools[m] = totals[3];
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace abom
+
+extern "C" int abom_remediation_cap(int which) {
+    switch (which) {
+        case 0: return abom::REMED_SRV_CAP;
+        case 1: return abom::REMED_AG_CAP;
+        case 2: return abom::REMED_CR_CAP;
+        case 3: return abom::REMED_TL_CAP;
+        case 4: return abom::REMED_T1_INSTALLS;
+        default: return -1;
+    }
+}
+
+extern "C" int abom_remediation_fold(
+    const void* pkg_idx, const void* win_idx, const void* scores, long long num_findings,
+    const void* item_of, const void* a_severity, const void* a_kev,
+    void* state, void* matched, void* counters, void* host_counters, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (num_findings >= (1ll << 31)) return (int)hipErrorInvalidValue;
+    if (num_findings > 0) {
+        const int block = 256;
+        hipLaunchKernelGGL(abom::remed_fold_kernel, dim3(abom::grid_for(num_findings, block)),
+                           dim3(block), 0, s,
+                           (const long long*)pkg_idx, (const long long*)win_idx,
+                           (const uint32_t*)scores, num_findings, (const int*)item_of,
+                           (const uint8_t*)a_severity, (const uint8_t*)a_kev,
+                           (uint32_t*)state, (uint32_t*)matched, (unsigned int*)counters);
+        ABOM_CHECK(hipGetLastError());
+    }
+    ABOM_CHECK(hipMemcpyAsync(host_counters, counters, 4 * sizeof(unsigned int),
+                              hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+extern "C" int abom_remediation_gather(
+    const void* items, long long num_items,
+    const void* pkg_idx, const void* win_idx, long long num_findings,
+    const void* w_flags, const void* w_fixed_hi, const void* w_fixed_lo, void* state,
+    void* out_rep_pkg, void* out_installs, void* out_findings, void* out_vulns,
+    void* out_score, void* out_sev, void* out_kev, void* out_fix_hi, void* out_fix_lo,
+    void* out_unfixed, void* stream) {
+    if (num_items <= 0) return 0;
+    hipLaunchKernelGGL(abom::remed_gather_kernel,
+                       dim3(abom::grid_for(num_items, abom::REMED_WAVES)), dim3(256), 0,
+                       (hipStream_t)stream,
+                       (const int*)items, num_items, (const long long*)pkg_idx,
+                       (const long long*)win_idx, num_findings, (const uint8_t*)w_flags,
+                       (const long long*)w_fixed_hi, (const long long*)w_fixed_lo,
+                       (uint32_t*)state, (int*)out_rep_pkg, (int*)out_installs,
+                       (int*)out_findings, (int*)out_vulns, (uint32_t*)out_score,
+                       (uint8_t*)out_sev, (uint8_t*)out_kev, (long long*)out_fix_hi,
+                       (long long*)out_fix_lo, (int*)out_unfixed);
+    return (int)hipGetLastError();
+}
+
+extern "C" int abom_remediation_scatter(
+    const void* pkg_idx, long long num_findings, const void* item_of, void* state,
+    const void* items_off, long long num_items, long long num_installs, void* csr_pkgs,
+    void* stream) {
+    if (num_findings <= 0 || num_items <= 0) return 0;
+    const int block = 256;
+    hipLaunchKernelGGL(abom::remed_scatter_kernel, dim3(abom::grid_for(num_findings, block)),
+                       dim3(block), 0, (hipStream_t)stream,
+                       (const long long*)pkg_idx, num_findings, (const int*)item_of,
+                       (uint32_t*)state, (const int*)items_off, num_items, num_installs,
+                       (int*)csr_pkgs);
+    return (int)hipGetLastError();
+}
+
+// The counters reach `host_counters` (pinned, four u32) through a copy on the
+// stream, and are zeroed behind it; the caller waits for the copy.
+extern "C" int abom_remediation_union(
+    const void* items, long long num_items, const void* items_off, const void* csr_pkgs,
+    long long pkg_base,
+    const void* rev_off, const void* rev_col, const void* rev_et, int et_contains,
+    const void* reach_off, const void* reach_col, long long row_base, long long num_rows,
+    long long node_span, void* state, void* queue, void* pool, long long pool_slices,
+    void* counters, void* host_counters,
+    void* out_servers, void* out_agents, void* out_creds, void* out_tools, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (pool_slices < 1 || node_span < 0 || node_span >= (1ll << 32)) return (int)hipErrorInvalidValue;
+    if (num_items > 0) {
+        abom::RemedGraph g;
+        g.rev_off = (const uint64_t*)rev_off;
+        g.rev_col = (const uint32_t*)rev_col;
+        g.rev_et = (const uint8_t*)rev_et;
+        g.et_contains = (uint8_t)et_contains;
+        g.pkg_base = pkg_base;
+        g.items_off = (const int*)items_off;
+        g.csr_pkgs = (const int*)csr_pkgs;
+        abom::HopIndex ix;
+        ix.reach_off = (const int4*)reach_off;
+        ix.reach_col = (const uint32_t*)reach_col;
+        ix.row_base = (uint32_t)row_base;
+        ix.num_rows = (uint32_t)num_rows;
+        ix.agent_off = nullptr;
+        ix.agent_srv = nullptr;
+        ix.num_agents = 0;
+        hipLaunchKernelGGL(abom::remed_union_wave_kernel,
+                           dim3(abom::grid_for(num_items, abom::REMED_WAVES)), dim3(256), 0, s,
+                           (const int*)items, num_items, g, ix, (uint32_t*)state,
+                           (uint32_t*)queue, (unsigned int*)counters,
+                           (int*)out_servers, (int*)out_agents, (int*)out_creds, (int*)out_tools);
+        ABOM_CHECK(hipGetLastError());
+        // the queue length is known on the device only: one block per slice,
+        // a block without a queued item leaves at once
+        const long long blocks = pool_slices < num_items ? pool_slices : num_items;
+        hipLaunchKernelGGL(abom::remed_union_block_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
+                           g, ix, (const uint32_t*)queue, (unsigned int*)counters,
+                           (uint32_t*)pool, (num_rows + 31) / 32, (node_span + 31) / 32,
+                           (uint32_t)node_span,
+                           (int*)out_servers, (int*)out_agents, (int*)out_creds, (int*)out_tools);
+        ABOM_CHECK(hipGetLastError());
+    }
+    ABOM_CHECK(hipMemcpyAsync(host_counters, counters, 4 * sizeof(unsigned int),
+                              hipMemcpyDeviceToHost, s));
+    ABOM_CHECK(hipMemsetAsync(counters, 0, 4 * sizeof(unsigned int), s));
+    return 0;
+}

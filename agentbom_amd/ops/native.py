@@ -183,6 +183,34 @@ _SIGNATURES = {
         _c, _c, _c,            # queue, counters, host_counters
         _c, _c, _c, _c, _c,    # out_hop_agents, out_creds, out_depth, out_overflow, stream
     ], _i32),
+    "abom_remediation_cap": ([_i32], _i32),  # which
+    "abom_remediation_fold": ([
+        _c, _c, _c, _i64,      # pkg_idx, win_idx, scores, num_findings
+        _c, _c, _c,            # item_of, a_severity, a_kev
+        _c, _c, _c, _c, _c,    # state, matched, counters, host_counters, stream
+    ], _i32),
+    "abom_remediation_gather": ([
+        _c, _i64,              # items, num_items
+        _c, _c, _i64,          # pkg_idx, win_idx, num_findings
+        _c, _c, _c, _c,        # w_flags, w_fixed_hi, w_fixed_lo, state
+        _c, _c, _c, _c,        # out_rep_pkg, out_installs, out_findings, out_vulns
+        _c, _c, _c, _c, _c,    # out_score, out_sev, out_kev, out_fix_hi, out_fix_lo
+        _c, _c,                # out_unfixed, stream
+    ], _i32),
+    "abom_remediation_scatter": ([
+        _c, _i64, _c, _c,      # pkg_idx, num_findings, item_of, state
+        _c, _i64, _i64, _c,    # items_off, num_items, num_installs, csr_pkgs
+        _c,                    # stream
+    ], _i32),
+    "abom_remediation_union": ([
+        _c, _i64, _c, _c,        # items, num_items, items_off, csr_pkgs
+        _i64,                    # pkg_base
+        _c, _c, _c, _i32,        # rev_off, rev_col, rev_et, et_contains
+        _c, _c, _i64, _i64,      # reach_off, reach_col, row_base, num_rows
+        _i64, _c, _c, _c, _i64,  # node_span, state, queue, pool, pool_slices
+        _c, _c,                  # counters, host_counters
+        _c, _c, _c, _c, _c,      # out_servers, out_agents, out_creds, out_tools, stream
+    ], _i32),
     "abom_path_relax": ([
         _c, _c, _c, _c,  # edge_src, col, etype, edge_weight
         _c, _c, _c, _c,  # cur, nxt, node_boost, etype_boost
@@ -1485,6 +1513,239 @@ def blast_hops_sized(pkgs32, n_dev, rev: dict, index: dict, agent_index: dict,
     done.synchronize()
     queued, n_overflow = host.tolist()
     return hop_agents, t_creds, hop_depth, overflow, queued, n_overflow
+
+
+# ── Remediation plan (ops/csrc/remediation.hip) ─────────────────────────────
+
+# LDS caps of remed_union_wave_kernel and the install count above which an
+# item goes straight to the bitmap tier (REMED_*, csrc/remediation.hip);
+# ``abom_remediation_cap`` reports the values the library was built with.
+REMEDIATION_SRV_CAP = 256
+REMEDIATION_AG_CAP = 256
+REMEDIATION_CR_CAP = 256
+REMEDIATION_TL_CAP = 512
+REMEDIATION_T1_INSTALLS = 1024
+# workspace tensors that are all-zero between calls
+REMEDIATION_ZERO_KEYS = ("remed_state", "remed_counters", "remed_pool")
+_REMED_POOL_BYTES = 256 << 20
+_REMED_POOL_SLICES = 256
+_WF_HAS_FIXED = 2
+
+
+def remediation_native_enabled() -> bool:
+    """A/B toggle: AGENT_BOM_REMEDIATION_NATIVE=0 makes
+    ``EstateEngine.remediation_plan`` compute the per-item arrays with the
+    exact torch join (:func:`remediation_items_join`) instead of the kernels
+    of csrc/remediation.hip."""
+    return os.environ.get("AGENT_BOM_REMEDIATION_NATIVE", "1") != "0"
+
+
+def _reach_node_span(index: dict) -> int:
+    """1 + the largest node id the reach index names, as a row or an entry;
+    read from the device once and kept on the index."""
+    span = index.get("node_span")
+    if span is None:
+        span = int(index["row_base"]) + index["reach_off"].shape[0]
+        if index["reach_col"].numel():
+            span = max(span, int(index["reach_col"].max().item()) + 1)
+        index["node_span"] = span
+    return span
+
+
+def _remediation_empty(torch, dev) -> dict:
+    from agentbom_amd.ops.cpu_ref import REMEDIATION_KEYS
+
+    dtypes = dict.fromkeys(REMEDIATION_KEYS, torch.int32)
+    dtypes.update(max_score=torch.float32, worst_sev=torch.uint8, kev=torch.uint8,
+                  fix_hi=torch.int64, fix_lo=torch.int64)
+    return {k: torch.empty(0, dtype=dtypes[k], device=dev) for k in REMEDIATION_KEYS}
+
+
+def remediation_items(pkg_idx, win_idx, scores, item_of, n_items: int, arena: dict,
+                      rev: dict, index: dict, et_contains: int, pkg_base: int,
+                      workspace: Optional[dict] = None,
+                      pool_slices: Optional[int] = None) -> dict:
+    """The per-item arrays of the remediation plan (csrc/remediation.hip;
+    semantics and keys: ``cpu_ref.remediation_plan``) for the findings
+    ``pkg_idx`` (int64, ascending), ``win_idx`` (int64) and ``scores`` (fp32,
+    >= 0).  ``item_of`` int32 [P] maps a package to one of ``n_items`` items,
+    ``index`` is the per-server reach index, which must hold a row for every
+    source of a CONTAINS edge.  Exact on the device: an item too large for
+    the LDS sets of the wave kernel is counted in a slice of a bitmap pool of
+    ``pool_slices`` slices (default: as many as fit 256 MiB, at most 256).
+
+    Two host reads: {matched items, matched installs} after the fold, to size
+    the outputs, and {tier-2 items, pool rounds} at the end, left as ints in
+    ``workspace["remed_queued"]`` and ``workspace["remed_rounds"]``.  The
+    workspace tensors named by ``REMEDIATION_ZERO_KEYS`` are all-zero before
+    and after a call."""
+    import torch
+
+    dev = pkg_idx.device
+    if dev.type != "cuda":
+        raise ValueError(f"remediation_items: pkg_idx on {dev}, expected a GPU tensor")
+    F = pkg_idx.numel()
+    _require(pkg_idx, "pkg_idx", torch.int64, dev)
+    _require(win_idx, "win_idx", torch.int64, dev, F)
+    _require(scores, "scores", torch.float32, dev, F)
+    _require(item_of, "item_of", torch.int32, dev)
+    _require(rev["row_off"], "rev.row_off", torch.int64, dev)
+    _require(rev["col"], "rev.col", torch.int32, dev)
+    _require(rev["etype"], "rev.etype", torch.uint8, dev, rev["col"].numel())
+    _require(index["reach_off"], "index.reach_off", torch.int32, dev)
+    _require(index["reach_col"], "index.reach_col", torch.int32, dev)
+    windows = arena["windows"]
+    W = windows["flags"].numel()
+    _require(windows["flags"], "windows.flags", torch.uint8, dev)
+    _require(windows["fixed_hi"], "windows.fixed_hi", torch.int64, dev, W)
+    _require(windows["fixed_lo"], "windows.fixed_lo", torch.int64, dev, W)
+    _require(arena["severity"], "arena.severity", torch.uint8, dev, W)
+    _require(arena["kev"], "arena.kev", torch.uint8, dev, W)
+    ws = workspace if workspace is not None else {}
+    ws["remed_queued"] = ws["remed_rounds"] = 0
+    if F == 0:
+        return _remediation_empty(torch, dev)
+    if F >= 1 << 31:
+        raise RuntimeError(f"remediation_items: {F} findings exceed int32")
+    lib = load()
+    rows = index["reach_off"].shape[0]
+    span = _reach_node_span(index)
+    slice_words = (rows + 31) // 32 + 3 * ((span + 31) // 32)
+    if pool_slices is None:
+        pool_slices = max(1, min(_REMED_POOL_SLICES, _REMED_POOL_BYTES // (4 * slice_words)))
+    if pool_slices < 1:
+        raise ValueError("remediation_items: pool_slices < 1")
+    state = _buf(ws, "remed_state", 8 * n_items, torch.int32, dev, zero=True)
+    counters = _buf(ws, "remed_counters", 4, torch.int32, dev, zero=True)
+    pool = _buf(ws, "remed_pool", pool_slices * slice_words, torch.int32, dev, zero=True)
+    matched = _buf(ws, "remed_matched", min(n_items, F), torch.int32, dev)
+    host = ws.get("remed_host_counters")
+    if host is None:
+        host = ws["remed_host_counters"] = torch.zeros(4, dtype=torch.int32, pin_memory=True)
+    rc = lib.abom_remediation_fold(
+        _ptr(pkg_idx), _ptr(win_idx), _ptr(scores), F,
+        _ptr(item_of), _ptr(arena["severity"]), _ptr(arena["kev"]),
+        _ptr(state), _ptr(matched), _ptr(counters), _ptr(host), _stream())
+    _check(rc, "abom_remediation_fold")
+    done = torch.cuda.Event()
+    done.record()
+    done.synchronize()  # the host read that sizes the outputs
+    M, _, _, NI = host.tolist()
+    items = torch.sort(matched[:M]).values
+    i32 = {k: torch.empty(M, dtype=torch.int32, device=dev)
+           for k in ("rep_pkg", "installs", "n_findings", "n_vulns", "max_score", "n_unfixed",
+                     "n_servers", "n_agents", "n_creds", "n_tools")}
+    u8 = {k: torch.empty(M, dtype=torch.uint8, device=dev) for k in ("worst_sev", "kev")}
+    i64 = {k: torch.empty(M, dtype=torch.int64, device=dev) for k in ("fix_hi", "fix_lo")}
+    rc = lib.abom_remediation_gather(
+        _ptr(items), M, _ptr(pkg_idx), _ptr(win_idx), F,
+        _ptr(windows["flags"]), _ptr(windows["fixed_hi"]), _ptr(windows["fixed_lo"]),
+        _ptr(state),
+        _ptr(i32["rep_pkg"]), _ptr(i32["installs"]), _ptr(i32["n_findings"]),
+        _ptr(i32["n_vulns"]), _ptr(i32["max_score"]), _ptr(u8["worst_sev"]), _ptr(u8["kev"]),
+        _ptr(i64["fix_hi"]), _ptr(i64["fix_lo"]), _ptr(i32["n_unfixed"]), _stream())
+    _check(rc, "abom_remediation_gather")
+    # item -> its matched installs as a CSR; order within an item is free
+    items_off = torch.zeros(M + 1, dtype=torch.int32, device=dev)
+    torch.cumsum(i32["installs"], 0, out=items_off[1:])
+    csr_pkgs = torch.empty(NI, dtype=torch.int32, device=dev)
+    rc = lib.abom_remediation_scatter(
+        _ptr(pkg_idx), F, _ptr(item_of), _ptr(state), _ptr(items_off), M, NI,
+        _ptr(csr_pkgs), _stream())
+    _check(rc, "abom_remediation_scatter")
+    queue = _buf(ws, "remed_queue", M, torch.int32, dev)
+    rc = lib.abom_remediation_union(
+        _ptr(items), M, _ptr(items_off), _ptr(csr_pkgs), int(pkg_base),
+        _ptr(rev["row_off"]), _ptr(rev["col"]), _ptr(rev["etype"]), int(et_contains),
+        _ptr(index["reach_off"]), _ptr(index["reach_col"]), int(index["row_base"]), rows,
+        span, _ptr(state), _ptr(queue), _ptr(pool), int(pool_slices),
+        _ptr(counters), _ptr(host),
+        _ptr(i32["n_servers"]), _ptr(i32["n_agents"]), _ptr(i32["n_creds"]),
+        _ptr(i32["n_tools"]), _stream())
+    _check(rc, "abom_remediation_union")
+    done.record()
+    done.synchronize()
+    _, ws["remed_queued"], ws["remed_rounds"], _ = host.tolist()
+    out = {"item": items, **i32, **u8, **i64}
+    out["max_score"] = out["max_score"].view(torch.float32)
+    return out
+
+
+def remediation_items_join(pkg_idx, win_idx, scores, item_of, arena: dict, rev: dict,
+                           index: dict, et_contains: int, pkg_base: int) -> dict:
+    """The outputs of :func:`remediation_items` as sort-based set operations
+    in torch on the tensors' device: (item position << 32 | node) pairs, then
+    ``unique``.  Exact for any set size; the comparison arm of
+    AGENT_BOM_REMEDIATION_NATIVE=0."""
+    import torch
+
+    dev = pkg_idx.device
+    F = pkg_idx.numel()
+    if F == 0:
+        return _remediation_empty(torch, dev)
+    sign = -0x8000000000000000
+    windows = arena["windows"]
+    W = windows["flags"].numel()
+    items, inv = torch.unique(item_of[pkg_idx].to(torch.int64), return_inverse=True)
+    M = items.numel()
+
+    def count(pos):
+        return torch.bincount(pos, minlength=M).to(torch.int32)
+
+    def reduce(src, how, init):
+        return torch.full((M,), init, dtype=src.dtype, device=dev).scatter_reduce_(
+            0, inv, src, how)
+
+    head = torch.ones(F, dtype=torch.bool, device=dev)
+    head[1:] = pkg_idx[1:] != pkg_idx[:-1]
+    out = {"item": items.to(torch.int32),
+           "rep_pkg": reduce(pkg_idx, "amin", 1 << 62).to(torch.int32),
+           "installs": count(inv[head]), "n_findings": count(inv)}
+    # distinct (item, window) pairs
+    iw = torch.unique(inv * W + win_idx)
+    m_iw, w_iw = iw // W, iw % W
+    out["n_vulns"] = count(m_iw)
+    # scores are >= 0, so 0 is neutral for the max
+    out["max_score"] = reduce(scores, "amax", 0.0)
+    out["worst_sev"] = reduce(arena["severity"][win_idx].to(torch.int64), "amax", 0).to(torch.uint8)
+    out["kev"] = reduce((arena["kev"][win_idx] != 0).to(torch.int64), "amax", 0).to(torch.uint8)
+    fixed = (windows["flags"][w_iw] & _WF_HAS_FIXED) != 0
+    # largest fixed key as unsigned 128 bits: the sign flip turns the int64
+    # order into the u64 order; the best hi first, then the best lo among them
+    m_fx = m_iw[fixed]
+    hi, lo = windows["fixed_hi"][w_iw[fixed]] ^ sign, windows["fixed_lo"][w_iw[fixed]] ^ sign
+    best_hi = torch.full((M,), sign, dtype=torch.int64, device=dev).scatter_reduce_(
+        0, m_fx, hi, "amax")
+    top = hi == best_hi[m_fx]
+    best_lo = torch.full((M,), sign, dtype=torch.int64, device=dev).scatter_reduce_(
+        0, m_fx[top], lo[top], "amax")
+    has = torch.bincount(m_fx, minlength=M) > 0
+    zero = torch.zeros(M, dtype=torch.int64, device=dev)
+    out["fix_hi"] = torch.where(has, best_hi ^ sign, zero)
+    out["fix_lo"] = torch.where(has, best_lo ^ sign, zero)
+    out["n_unfixed"] = count(m_iw[~fixed])
+    # (item, server): the CONTAINS sources of the matched installs
+    nodes = pkg_idx[head] + int(pkg_base)
+    beg = rev["row_off"][nodes]
+    e, carry = _hops_expand(torch, beg, rev["row_off"][nodes + 1] - beg, inv[head],
+                            torch.arange(rev["col"].numel(), device=dev))
+    held = rev["etype"][e] == et_contains
+    ms = torch.unique((carry[held] << 32) | rev["col"][e[held]].to(torch.int64))
+    out["n_servers"] = count(ms >> 32)
+    reach_off = index["reach_off"].to(torch.int64)
+    S = reach_off.shape[0]
+    row = (ms & 0xFFFFFFFF) - int(index["row_base"])
+    ok = (row >= 0) & (row < S)
+    row = row.clamp(0, max(S - 1, 0))
+    for seg, key in enumerate(("n_agents", "n_creds", "n_tools")):
+        if S == 0:
+            out[key] = torch.zeros(M, dtype=torch.int32, device=dev)
+            continue
+        sbeg = reach_off[row, seg]
+        cnt = torch.where(ok, reach_off[row, seg + 1] - sbeg, torch.zeros_like(sbeg))
+        nbr, pos = _hops_expand(torch, sbeg, cnt, ms >> 32, index["reach_col"])
+        out[key] = count(torch.unique((pos << 32) | nbr) >> 32)
+    return out
 
 
 def risk_weights_array() -> np.ndarray:
