@@ -59,6 +59,14 @@ construction) and stays resident in HBM3E.  On top of it:
                          bitmap pool for the zipf heads;
                          AGENT_BOM_REMEDIATION_NATIVE=0 runs an exact torch
                          join instead)
+- ``toxic_combinations()`` the pattern layer: per finding the risks that
+                         are critical together (creds, KEV, execute or
+                         retrieval tools, a shared server, an advisory across
+                         three agents) with their score, per advisory its
+                         findings, packages, servers and agents, and the
+                         shared servers with a write and a read tool; a
+                         per-server capability table, a fold per finding and
+                         the set unions of ops/csrc/toxic.hip
 - ``blast_radius_query()`` batched bounded BFS for p50 query latency /
                          the /v1/graph read path
 - ``pagerank()`` / ``betweenness()`` / ``choke_points()`` centrality on
@@ -580,6 +588,11 @@ class EstateEngine:
         # use, and the workspace of ops/csrc/remediation.hip
         self._remed_items = None
         self._remed_ws: dict = {}
+        # toxic combinations: the workspace of ops/csrc/toxic.hip, the server
+        # table of the last caps tensor and the count of the last advisory map
+        self._toxic_ws: dict = {}
+        self._toxic_cache = None
+        self._toxic_vuln_cache = None
 
     def _build_csr(self, src, dst, et):
         """GPU CSR construction: stable sort by src, bincount offsets."""
@@ -1154,6 +1167,145 @@ class EstateEngine:
         plan["agents_pct"] = pct[order]
         plan["n_items"] = n_matched
         return plan
+
+    def _toxic_caps(self, tool_caps):
+        """(tool_caps uint8 [n_tools] on the device, its server table, its
+        poison servers): the table and the poison servers depend on the graph
+        and the caps alone, so they are kept for the last caps tensor seen
+        (None: all-zero caps) until it is replaced or written to."""
+        torch = self.torch
+        key = None if tool_caps is None else (tool_caps.data_ptr(), tool_caps._version)
+        cached = self._toxic_cache
+        if cached is not None and cached["key"] == key:
+            return cached["caps"], cached["table"], cached["poison"]
+        n_tools = self.estate.n_tools
+        if tool_caps is None:
+            caps = torch.zeros(n_tools, dtype=torch.uint8, device=self.device)
+        else:
+            if tool_caps.dtype != torch.uint8:
+                raise TypeError(f"tool_caps: expected torch.uint8, got {tool_caps.dtype}")
+            if tool_caps.numel() != n_tools:
+                raise ValueError(f"tool_caps: {tool_caps.numel()} elements, expected {n_tools}")
+            caps = tool_caps.to(self.device).contiguous()
+        table = poison = None
+        if self.use_gpu:
+            from agentbom_amd.ops import native
+
+            table = native.toxic_server_table(self.reach_index, caps, self.tool_is_db,
+                                              self.estate.tool_base)
+            poison = native.toxic_poison_servers(table, self.reach_index["row_base"])
+        # the caller's tensor is kept with the key: its address stays its own
+        self._toxic_cache = {"key": key, "held": tool_caps, "caps": caps, "table": table,
+                             "poison": poison}
+        return caps, table, poison
+
+    def _toxic_vuln_of(self, vuln_of):
+        """(vuln_of int32 [W] on the device or None, number of advisories);
+        the count of a map is read from it once and kept while the same
+        tensor comes back."""
+        torch = self.torch
+        W = self.arena["severity"].numel()
+        if vuln_of is None:
+            return None, W
+        if vuln_of.dtype != torch.int32:
+            raise TypeError(f"vuln_of: expected torch.int32, got {vuln_of.dtype}")
+        if vuln_of.numel() != W:
+            raise ValueError(f"vuln_of: {vuln_of.numel()} elements, expected {W}")
+        key = (vuln_of.data_ptr(), vuln_of._version)
+        cached = self._toxic_vuln_cache
+        if cached is None or cached["key"] != key:
+            on_dev = vuln_of.to(self.device).contiguous()
+            if W and int(on_dev.min()) < 0:
+                raise ValueError("vuln_of: negative advisory index")
+            cached = self._toxic_vuln_cache = {
+                "key": key, "held": vuln_of, "map": on_dev,
+                "n": int(on_dev.max()) + 1 if W else 0}
+        return cached["map"], cached["n"]
+
+    def toxic_combinations(self, step_res=None, tool_caps=None, vuln_of=None,
+                           k: Optional[int] = 100) -> dict:
+        """Toxic combinations of a step's findings: risks that are tolerable
+        alone and critical together -- a critical or high CVE with exposed
+        credentials, a KEV with credentials, a CVE behind an execute-capable
+        or a retrieval tool, a CVE on a server that agents share, one
+        advisory that reaches three or more agents -- per finding and per
+        advisory, and the shared servers with a write and a read tool.
+        Semantics, bits and scores: ``cpu_ref.toxic_combinations``.
+
+        ``tool_caps`` uint8 [estate.n_tools] gives the ``cpu_ref.TC_*``
+        capability bits of every tool (``toxic_combos.tool_caps_from_labels``
+        derives them from tool names); None means no capabilities: the tool
+        patterns and ``poison_servers`` are then empty.  ``vuln_of`` int32 [W]
+        maps an advisory window to its advisory (default: a window is one).
+
+        Returns tensors on the engine's device.  Aligned with ``step_res``:
+        ``patterns`` uint8 and ``combo_score`` fp32; ``order`` int64, the
+        findings with a pattern by combo_score descending, then finding index
+        ascending, the first ``k`` (all with ``k=None``).  Under ``vulns``
+        the arrays of ``cpu_ref.TOXIC_VULN_KEYS`` per matched advisory, the
+        first ``k`` in the order max_score descending, n_agents descending,
+        vuln ascending.  ``pkg_idx`` and ``win_idx`` are the step's,
+        ``vuln_of`` the map on the device or None, for
+        ``toxic_combos.estate_combinations``.  ``poison_servers`` int32 node
+        ids, ascending;
+        ``n_by_pattern`` int64 [6]; and as ints ``n_vulns`` (matched
+        advisories) and ``n_multi_agent``.  On the GPU from the kernels of
+        ops/csrc/toxic.hip, on the CPU from the oracle.  Calls :meth:`step`
+        when ``step_res`` is None."""
+        torch = self.torch
+        from agentbom_amd.ops import cpu_ref
+
+        if step_res is None:
+            step_res = self.step()
+        caps, table, poison = self._toxic_caps(tool_caps)
+        vmap, n_vulns = self._toxic_vuln_of(vuln_of)
+        pkg_idx, win_idx, scores = step_res["pkg_idx"], step_res["win_idx"], step_res["scores"]
+        if self.use_gpu:
+            from agentbom_amd.ops import native
+
+            res = native.toxic_combinations(
+                pkg_idx.contiguous(), win_idx.contiguous(), scores.contiguous(),
+                step_res["n_creds"].contiguous(), self.arena, self.tool_lut, table, self.rev,
+                self.reach_index, ET_CONTAINS, self.estate.pkg_base, vuln_of=vmap,
+                n_vulns=n_vulns, workspace=self._toxic_ws)
+            patterns, combo, per = res["patterns"], res["combo_score"], res["vulns"]
+            # a finding with a pattern scores above 0, one without scores 0:
+            # the stable descending sort puts the flagged ones first, by index
+            order = torch.argsort(combo, descending=True, stable=True)[:res["n_flagged"]]
+            # stable sorts from the last key up; positions are in vuln order
+            v_order = torch.argsort(per["n_agents"], descending=True, stable=True)
+            v_order = v_order[torch.argsort(per["max_score"][v_order], descending=True,
+                                            stable=True)]
+            n_by_pattern = torch.tensor(res["n_by_pattern"], dtype=torch.int64).to(self.device)
+            n_multi = res["n_multi_agent"]
+        else:
+            ref = cpu_ref.toxic_combinations(
+                pkg_idx.numpy(), win_idx.numpy(), scores.numpy(), step_res["n_creds"].numpy(),
+                step_res["n_tools"].numpy(),
+                self.rev["row_off"].numpy(), self.rev["col"].numpy(), self.rev["etype"].numpy(),
+                self.fwd["row_off"].numpy(), self.fwd["col"].numpy(), self.fwd["etype"].numpy(),
+                ET_CONTAINS, ET_USES, ET_PROVIDES_TOOL, self.estate.pkg_base,
+                self.arena["severity"].numpy(), self.arena["kev"].numpy(),
+                self.arena["impact"].numpy(), self.tool_lut.numpy(), self.estate.tool_base,
+                self.tool_is_db.numpy(), caps.numpy(),
+                None if vmap is None else vmap.numpy())
+            patterns = torch.from_numpy(ref["patterns"])
+            combo = torch.from_numpy(ref["combo_score"])
+            per = {key: torch.from_numpy(ref["vulns"][key]) for key in cpu_ref.TOXIC_VULN_KEYS}
+            flagged = torch.nonzero(patterns).flatten()
+            order = flagged[torch.argsort(combo[flagged], descending=True, stable=True)]
+            v_order = torch.from_numpy(ref["vulns"]["order"])
+            poison = torch.from_numpy(ref["poison_servers"])
+            n_by_pattern = torch.from_numpy(ref["n_by_pattern"])
+            n_multi = ref["n_multi_agent"]
+        n_matched = v_order.numel()
+        if k is not None:
+            order, v_order = order[:max(int(k), 0)], v_order[:max(int(k), 0)]
+        return {"patterns": patterns, "combo_score": combo, "order": order,
+                "pkg_idx": pkg_idx, "win_idx": win_idx, "vuln_of": vmap,
+                "vulns": {key: value[v_order] for key, value in per.items()},
+                "poison_servers": poison, "n_by_pattern": n_by_pattern,
+                "n_vulns": n_matched, "n_multi_agent": n_multi}
 
     def _score_cpu(self, counts, pos, pkg_nodes, win_idx, dist):
         """CPU oracle of the fused score_gather kernel: (scores, n_agents,

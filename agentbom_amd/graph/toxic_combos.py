@@ -155,3 +155,63 @@ def toxic_combination_to_finding(combo: ToxicCombination) -> Finding:
         is_actionable=True,
         id=combo.id,
     )
+
+
+# ── estate engine: capability bits of tools, and the API view of a result ───
+
+# keyword classes of the reference's tool-capability checks, per TC_* bit
+_CAP_KEYWORDS = (
+    ("TC_EXEC", ("execute", "run", "shell", "eval")),
+    ("TC_WRITE", ("write", "insert", "store", "save", "create", "upsert", "embed")),
+    ("TC_DELETE", ("delete", "destroy")),
+    ("TC_READ", ("read", "search", "query", "fetch", "get", "lookup")),
+    ("TC_RETRIEVAL", ("similarity", "semantic", "retriev*", "embedding", "vector", "rag")),
+)
+
+
+def _keyword_match(keyword: str, text: str) -> bool:
+    """``keyword`` as a whole word of ``text`` (a trailing ``*`` allows any
+    word ending), with underscores, hyphens and dots read as spaces: "run"
+    matches "run_command" and "run-task" but not "runner"."""
+    import re
+
+    normalized = re.sub(r"[_\-.]", " ", text)
+    if keyword.endswith("*"):
+        return bool(re.search(rf"\b{re.escape(keyword[:-1])}\w*\b", normalized))
+    return bool(re.search(rf"\b{re.escape(keyword)}\b", normalized))
+
+
+def tool_caps_from_labels(labels):
+    """``tool_caps`` uint8 [len(labels)] for ``EstateEngine.toxic_combinations``:
+    the ``cpu_ref.TC_*`` bits of every tool, from its name or description by
+    the reference's keyword classes, matched on word boundaries in lower case."""
+    import numpy as np
+
+    from agentbom_amd.ops import cpu_ref
+
+    caps = np.zeros(len(labels), dtype=np.uint8)
+    for i, label in enumerate(labels):
+        text = str(label).lower()
+        for name, keywords in _CAP_KEYWORDS:
+            if any(_keyword_match(kw, text) for kw in keywords):
+                caps[i] |= getattr(cpu_ref, name)
+    return caps
+
+
+def estate_combinations(result: dict, k: int = 100) -> list[dict[str, Any]]:
+    """The top ``k`` findings of an ``EstateEngine.toxic_combinations`` result
+    as plain dicts for the API layer, in the result's order: ``finding``
+    index, ``package`` index, ``advisory`` (the window, or what ``vuln_of``
+    maps it to), ``patterns`` names and ``score``."""
+    from agentbom_amd.ops.cpu_ref import TOXIC_PATTERN_NAMES
+
+    order = result["order"][:max(int(k), 0)]
+    wins = result["win_idx"][order]
+    vuln_of = result.get("vuln_of")
+    advisories = wins if vuln_of is None else vuln_of[wins]
+    rows = zip(order.tolist(), result["pkg_idx"][order].tolist(), advisories.tolist(),
+               result["patterns"][order].tolist(), result["combo_score"][order].tolist())
+    return [{"finding": f, "package": p, "advisory": v,
+             "patterns": [name for b, name in enumerate(TOXIC_PATTERN_NAMES) if bits >> b & 1],
+             "score": score}
+            for f, p, v, bits, score in rows]

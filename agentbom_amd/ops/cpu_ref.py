@@ -591,3 +591,171 @@ def remediation_plan(pkg_idx, win_idx, scores, item_of,
         sorted(range(M), key=lambda m: (-float(res["max_score"][m]), -int(res["n_agents"][m]),
                                         int(res["item"][m]))), dtype=np.int64)
     return res
+
+
+# ── toxic combinations (oracle for csrc/toxic.hip) ──────────────────────────
+
+# tool capability bits of ``tool_caps``
+TC_EXEC, TC_WRITE, TC_DELETE, TC_READ, TC_RETRIEVAL = 1, 2, 4, 8, 16
+TC_DANGEROUS = TC_EXEC | TC_WRITE | TC_DELETE
+# pattern bits of a finding, in the order of ``n_by_pattern``
+TP_CRED_BLAST, TP_KEV_WITH_CREDS, TP_EXECUTE_EXPLOIT = 1, 2, 4
+TP_CACHE_POISON, TP_LATERAL_CHAIN, TP_MULTI_AGENT_CVE = 8, 16, 32
+TOXIC_PATTERN_NAMES = ("cred_blast", "kev_with_credentials", "execute_exploit",
+                       "cache_poison", "lateral_chain", "multi_agent_cve")
+# per pattern bit: (fp32 multiplier of the score, default without a score)
+TOXIC_SCORING = ((1.5, 9.0), (None, 10.0), (1.3, 8.5), (1.5, 9.5), (1.4, 9.0), (1.2, 7.5))
+TOXIC_HOT_SEVERITY = 4      # high; 5 is critical
+TOXIC_MULTI_AGENTS = 3      # agents of one advisory from which it is multi-agent
+# the per-advisory arrays, in the order they are documented
+TOXIC_VULN_KEYS = ("vuln", "n_findings", "n_packages", "n_servers", "n_agents", "max_score",
+                   "worst_sev", "kev", "patterns")
+
+
+def _toxic_score(bit_index: int, s) -> np.float32:
+    """One fp32 multiply by an fp32 constant, then a min: nothing to fuse."""
+    mult, default = TOXIC_SCORING[bit_index]
+    if mult is None or not s > 0:
+        return np.float32(default)
+    return min(np.float32(s) * np.float32(mult), np.float32(10.0))
+
+
+def toxic_combinations(pkg_idx, win_idx, scores, n_creds, n_tools,
+                       rev_off, rev_col, rev_et, fwd_off, fwd_col, fwd_et,
+                       et_contains: int, et_uses: int, et_tool: int, pkg_base: int,
+                       a_severity, a_kev, a_impact, tool_lut, tool_base: int,
+                       tool_is_db, tool_caps, vuln_of=None) -> dict:
+    """Toxic combinations of a step's findings, from the definitions: risks
+    that are tolerable alone and critical together (the reference's
+    ``toxic_combos.py``, per finding and per advisory).
+
+    For finding f with package p, window w, ``hot`` = a_severity[w] >= 4 and
+    advisory v = vuln_of[w] (w itself without a map): the servers of p are the
+    distinct CONTAINS sources of node p + pkg_base, the agents of a server its
+    distinct USES sources, and ``exposed`` the OR of ``tool_caps`` (u8
+    [n_tools], indexed by node - tool_base) over the PROVIDES_TOOL targets of
+    those servers -- all of them at tool_lut[a_impact[w]] == 2, those with
+    ``tool_is_db`` at 1, none at 0, the filter of the step's ``n_tools``
+    (a finding that exposes a capability with n_tools[f] == 0 is refused).
+    ``patterns`` u8 [F]: TP_CRED_BLAST hot and n_creds[f] > 0;
+    TP_KEV_WITH_CREDS a_kev[w] and n_creds[f] > 0; TP_EXECUTE_EXPLOIT hot and
+    exposed & TC_DANGEROUS; TP_CACHE_POISON hot and exposed & TC_RETRIEVAL;
+    TP_LATERAL_CHAIN hot and a server of p has >= 2 agents;
+    TP_MULTI_AGENT_CVE, at any severity, v has >= 3 distinct agents over the
+    servers of all packages of all its findings.  ``combo_score`` fp32 [F]:
+    the largest of the set bits' scores (``TOXIC_SCORING``: min(s * mult, 10)
+    with s = scores[f], for the multi-agent bit s = the advisory's largest
+    score; the default where s is not > 0), 0.0 without a bit.  The reference
+    scales the first blast radius it met; the advisory's maximum is used here
+    because it does not depend on order.
+
+    Returns ``patterns`` and ``combo_score`` per finding and, under ``vulns``,
+    per advisory with a finding, ascending (``TOXIC_VULN_KEYS``): ``vuln``,
+    ``n_findings``, ``n_packages``, ``n_servers``, ``n_agents`` int32,
+    ``max_score`` fp32, ``worst_sev``, ``kev`` and ``patterns`` (OR over its
+    findings) u8; ``order`` int64, the positions by max_score descending,
+    n_agents descending, vuln ascending.  On top: ``poison_servers`` int32: the nodes
+    with >= 2 agents whose unfiltered tool caps hold TC_WRITE and TC_READ or
+    TC_RETRIEVAL (the reference's cross-agent poison), ascending.
+    ``n_by_pattern`` int64 [6] findings per bit, ``n_multi_agent`` the number
+    of multi-agent advisories.
+
+    Out of scope: TRANSITIVE_CRITICAL (the estate has no direct/transitive
+    flag), the keyword text of titles, deduplication by title."""
+    pkg_idx = np.asarray(pkg_idx, dtype=np.int64)
+    win_idx = np.asarray(win_idx, dtype=np.int64)
+    scores = np.asarray(scores, dtype=np.float32)
+    F = len(pkg_idx)
+    num_nodes = len(rev_off) - 1
+    n_tool_nodes = len(tool_caps)
+
+    def row(off, col, et, node, want):
+        return {int(col[e]) for e in range(int(off[node]), int(off[node + 1])) if et[e] == want}
+
+    def caps_of(server, db_only=False):
+        caps = 0
+        for t in row(fwd_off, fwd_col, fwd_et, server, et_tool):
+            k = t - tool_base
+            if 0 <= k < n_tool_nodes and (not db_only or tool_is_db[k]):
+                caps |= int(tool_caps[k])
+        return caps
+
+    patterns = np.zeros(F, dtype=np.uint8)
+    by_vuln: dict = {}
+    for f in range(F):
+        p, w = int(pkg_idx[f]), int(win_idx[f])
+        servers = row(rev_off, rev_col, rev_et, p + pkg_base, et_contains)
+        cls = int(tool_lut[a_impact[w]])
+        exposed = 0
+        for s in servers:
+            exposed |= caps_of(s, db_only=cls == 1) if cls else 0
+        if exposed and not n_tools[f] > 0:
+            raise ValueError(f"finding {f} exposes a tool capability with n_tools == 0")
+        hot = int(a_severity[w]) >= TOXIC_HOT_SEVERITY
+        creds = n_creds[f] > 0
+        shared = any(len(row(rev_off, rev_col, rev_et, s, et_uses)) >= 2 for s in servers)
+        bits = 0
+        if hot and creds:
+            bits |= TP_CRED_BLAST
+        if a_kev[w] and creds:
+            bits |= TP_KEV_WITH_CREDS
+        if hot and exposed & TC_DANGEROUS:
+            bits |= TP_EXECUTE_EXPLOIT
+        if hot and exposed & TC_RETRIEVAL:
+            bits |= TP_CACHE_POISON
+        if hot and shared:
+            bits |= TP_LATERAL_CHAIN
+        patterns[f] = bits
+        by_vuln.setdefault(w if vuln_of is None else int(vuln_of[w]), []).append(f)
+
+    per = {k: [] for k in TOXIC_VULN_KEYS}
+    for v in sorted(by_vuln):
+        fs = by_vuln[v]
+        pkgs = {int(pkg_idx[f]) for f in fs}
+        servers: set = set()
+        for p in pkgs:
+            servers |= row(rev_off, rev_col, rev_et, p + pkg_base, et_contains)
+        agents: set = set()
+        for s in servers:
+            agents |= row(rev_off, rev_col, rev_et, s, et_uses)
+        if len(agents) >= TOXIC_MULTI_AGENTS:
+            for f in fs:
+                patterns[f] |= TP_MULTI_AGENT_CVE
+        bits = 0
+        for f in fs:
+            bits |= int(patterns[f])
+        for key, value in zip(TOXIC_VULN_KEYS, (
+                v, len(fs), len(pkgs), len(servers), len(agents), max(scores[f] for f in fs),
+                max(int(a_severity[win_idx[f]]) for f in fs),
+                int(any(a_kev[win_idx[f]] for f in fs)), bits)):
+            per[key].append(value)
+    dtypes = dict.fromkeys(TOXIC_VULN_KEYS, np.int32)
+    dtypes.update(max_score=np.float32, worst_sev=np.uint8, kev=np.uint8, patterns=np.uint8)
+    vulns = {k: np.asarray(per[k], dtype=dtypes[k]) for k in TOXIC_VULN_KEYS}
+    vuln_max = dict(zip(vulns["vuln"].tolist(), vulns["max_score"]))
+
+    combo = np.zeros(F, dtype=np.float32)
+    for f in range(F):
+        v = int(win_idx[f]) if vuln_of is None else int(vuln_of[win_idx[f]])
+        for b in range(6):
+            if patterns[f] >> b & 1:
+                s = vuln_max[v] if 1 << b == TP_MULTI_AGENT_CVE else scores[f]
+                combo[f] = max(combo[f], _toxic_score(b, s))
+    M = len(vulns["vuln"])
+    vulns["order"] = np.asarray(
+        sorted(range(M), key=lambda m: (-float(vulns["max_score"][m]),
+                                        -int(vulns["n_agents"][m]), int(vulns["vuln"][m]))),
+        dtype=np.int64)
+    poison = []
+    for s in range(num_nodes):
+        if len(row(rev_off, rev_col, rev_et, s, et_uses)) >= 2:
+            caps = caps_of(s)
+            if caps & TC_WRITE and caps & (TC_READ | TC_RETRIEVAL):
+                poison.append(s)
+    return {
+        "patterns": patterns, "combo_score": combo, "vulns": vulns,
+        "poison_servers": np.asarray(poison, dtype=np.int32),
+        "n_by_pattern": np.asarray(
+            [int(np.count_nonzero(patterns >> b & 1)) for b in range(6)], dtype=np.int64),
+        "n_multi_agent": int(np.count_nonzero(vulns["n_agents"] >= TOXIC_MULTI_AGENTS)),
+    }

@@ -234,6 +234,57 @@ int abom_remediation_union(
     void* counters, void* host_counters,
     void* out_servers, void* out_agents, void* out_creds, void* out_tools, void* stream);
 
+// toxic.hip (toxic combinations per finding and per advisory.
+// abom_toxic_server_table fills table u32 [num_rows] = caps_all | caps_db << 8
+// | shared << 16 per reach-index row from tool_caps and tool_is_db, u8
+// [num_tools] indexed by node id - tool_base.  Then five calls on one stream:
+// state is u32 [num_vulns, 8], pool u32 [pool_slices * ((num_rows + 31) / 32
+// + (node_span + 31) / 32)], counters u32 [16] = {matched advisories, tier-2
+// advisories, pool rounds, (package, advisory) heads, findings per pattern x
+// 6, multi-agent advisories, findings with a pattern, 0...}, all three
+// all-zero on entry and after abom_toxic_finish; host_counters is pinned host
+// u32 [16]: the fold writes its first four words, the finish all.  pkg_idx
+// and win_idx are int64 [num_findings], pkg_idx ascending, scores fp32,
+// n_creds int32; vuln_of is int32 [num_windows] or null for the identity map;
+// vulns is the sorted `matched` list, vulns_off the exclusive prefix of
+// out_packages with the total at [num_matched].  abom_toxic_cap returns a cap
+// of the wave kernel, not a hipError_t: 0 = servers, 1 = agents, 2 = the
+// package count above which an advisory skips the wave kernel, else -1)
+int abom_toxic_cap(int which);
+int abom_toxic_server_table(
+    const void* reach_off, const void* reach_col, long long num_rows,
+    const void* tool_caps, const void* tool_is_db, long long tool_base, long long num_tools,
+    void* table, void* stream);
+int abom_toxic_fold(
+    const void* pkg_idx, const void* win_idx, const void* scores, const void* n_creds,
+    long long num_findings, const void* vuln_of, long long num_windows, long long num_vulns,
+    const void* a_severity, const void* a_kev, const void* a_impact, const void* tool_lut,
+    const void* rev_off, const void* rev_col, const void* rev_et, int et_contains,
+    long long pkg_base, const void* table, long long row_base, long long num_rows,
+    void* state, void* matched, void* counters, void* host_counters, void* out_patterns,
+    void* stream);
+int abom_toxic_gather(
+    const void* vulns, long long num_matched, void* state,
+    void* out_findings, void* out_packages, void* out_score, void* out_sev, void* out_kev,
+    void* out_patterns, void* stream);
+int abom_toxic_scatter(
+    const void* pkg_idx, const void* win_idx, long long num_findings,
+    const void* vuln_of, long long num_windows, long long num_vulns, void* state,
+    const void* vulns_off, long long num_matched, long long num_heads, void* csr_pkgs,
+    void* stream);
+int abom_toxic_union(
+    long long num_matched, const void* vulns_off, const void* csr_pkgs, long long pkg_base,
+    const void* rev_off, const void* rev_col, const void* rev_et, int et_contains,
+    const void* reach_off, const void* reach_col, long long row_base, long long num_rows,
+    long long node_span, void* queue, void* pool, long long pool_slices, void* counters,
+    void* out_servers, void* out_agents, void* stream);
+int abom_toxic_finish(
+    const void* pkg_idx, const void* win_idx, const void* scores, long long num_findings,
+    const void* vuln_of, long long num_windows, long long num_vulns,
+    const void* vulns, long long num_matched, void* state,
+    const void* v_agents, const void* v_score, void* v_patterns,
+    void* patterns, void* combo_score, void* counters, void* host_counters, void* stream);
+
 // paths.hip (edge_weight and node_gate are nullable)
 int abom_path_relax(
     const void* edge_src, const void* col, const void* etype, const void* edge_weight,

@@ -1,6 +1,7 @@
 // Capped distinct sets in LDS, one per wave, over the per-server reach index
 // and the per-agent server index (gfx950, wave64).  Shared by the multi-hop
-// expansion (blast_hops.hip) and the remediation unions (remediation.hip).
+// expansion (blast_hops.hip) and, through abom_union.h, the remediation and
+// toxic-combination unions (remediation.hip, toxic.hip).
 // Every helper here must be reached by all lanes of the wave.
 #pragma once
 

@@ -31,6 +31,7 @@
 //   whether it was new.  A block walks its item twice, the second time
 //   clearing what the first set, so a slice is all-zero whenever a block
 //   leaves an item, and block b takes the queued items b, b + slices, ...
+//   The set walks of both tiers live in abom_union.h, shared with toxic.hip.
 //   Tier 1 also returns slot and cursor to 0: `state`, `pool` and `counters`
 //   are all-zero on return.
 //
@@ -45,7 +46,7 @@
 // server list, 4 KiB per block.
 
 #include "abom_api.h"
-#include "abom_sets.h"
+#include "abom_union.h"
 
 namespace abom {
 
@@ -53,11 +54,11 @@ constexpr int REMED_SRV_CAP = 256;
 constexpr int REMED_AG_CAP = 256;
 constexpr int REMED_CR_CAP = 256;
 constexpr int REMED_TL_CAP = 512;
-constexpr int REMED_WAVES = 4;
+constexpr int REMED_WAVES = UNION_WAVES;
 // an item with more installs than this skips tier 1: on an estate that
 // spreads installs over its servers it would pass the server cap anyway
 constexpr int REMED_T1_INSTALLS = 4 * REMED_SRV_CAP;
-constexpr int REMED_T2_LIST = 1024;
+constexpr int REMED_T2_LIST = UNION_T2_LIST;
 constexpr int REMED_ROW = 8;  // u32 words per item of `state`
 
 enum RemedWord { RW_FINDINGS, RW_INSTALLS, RW_SCORE, RW_SEV, RW_KEV, RW_HEAD, RW_SLOT, RW_CURSOR };
@@ -211,15 +212,7 @@ __global__ void __launch_bounds__(256) remed_scatter_kernel(
     }
 }
 
-struct RemedGraph {
-    const uint64_t* rev_off;
-    const uint32_t* rev_col;
-    const uint8_t* rev_et;
-    uint8_t et_contains;
-    long long pkg_base;
-    const int* items_off;   // [M + 1]
-    const int* csr_pkgs;    // package indices, grouped by matched item
-};
+using RemedGraph = UnionGraph;
 
 // Tier 1: one wave per matched item.
 __global__ void __launch_bounds__(256) remed_union_wave_kernel(
@@ -253,21 +246,8 @@ __global__ void __launch_bounds__(256) remed_union_wave_kernel(
         const int n_inst = g.items_off[m + 1] - beg;
         int n_srv = 0, n_ag = 0, n_cr = 0, n_tl = 0;
         bool ok = n_inst <= REMED_T1_INSTALLS;
-        // the distinct sources of CONTAINS edges into the installs, one
-        // install per lane, the k-th edge of every lane's reverse row at a time
-        for (int base = 0; base < n_inst && ok; base += 64) {
-            uint64_t e = 0, e_end = 0;
-            if (base + lane < n_inst) {
-                const long long node = g.pkg_base + g.csr_pkgs[beg + base + lane];
-                e = g.rev_off[node];
-                e_end = g.rev_off[node + 1];
-            }
-            for (; ok && __ballot(e < e_end); ++e) {
-                const bool valid = e < e_end && g.rev_et[e] == g.et_contains;
-                const uint32_t v = valid ? g.rev_col[e] : 0u;
-                ok = append_distinct(srv, n_srv, REMED_SRV_CAP, v, valid, stage, lane);
-            }
-        }
+        // the distinct sources of CONTAINS edges into the installs
+        ok = ok && collect_servers(g, beg, n_inst, srv, n_srv, REMED_SRV_CAP, stage, lane);
         ok = ok && expand_append<AGENTS_OF_SERVER>(ix, srv, 0, n_srv, lds_ag[wid], n_ag,
                                                   REMED_AG_CAP, t_beg, t_pref, stage, lane);
         ok = ok && expand_append<CREDS_OF_SERVER>(ix, srv, 0, n_srv, lds_cr[wid], n_cr,
@@ -285,68 +265,7 @@ __global__ void __launch_bounds__(256) remed_union_wave_kernel(
     }
 }
 
-struct RemedSlice {
-    uint32_t* srv;        // one bit per reach-index row
-    uint32_t* planes;     // agents, creds, tools: plane_words each, one bit per node id
-    long long plane_words;
-    uint32_t node_span;
-};
-
-// The index row `r`, entries start, start + step, ...: set and count new bits
-// (CLEAR = false) or return their words to zero.
-template <bool CLEAR>
-__device__ __forceinline__ void visit_row(const HopIndex& ix, const RemedSlice& sl, uint32_t r,
-                                          int start, int step, int3& fresh) {
-    const int4 off = ix.reach_off[r];
-    for (int t = off.x + start; t < off.w; t += step) {
-        const uint32_t v = ix.reach_col[t];
-        if (v >= sl.node_span) continue;  // not reached: node_span covers reach_col
-        const int kind = t < off.y ? 0 : t < off.z ? 1 : 2;
-        uint32_t* word = sl.planes + kind * sl.plane_words + (v >> 5);
-        if (CLEAR) {
-            *word = 0;
-        } else if (!(atomicOr(word, 1u << (v & 31)) & (1u << (v & 31)))) {
-            fresh.x += kind == 0;
-            fresh.y += kind == 1;
-            fresh.z += kind == 2;
-        }
-    }
-}
-
-// One walk of item m by the block: per chunk of 256 installs, a thread marks
-// the servers of its install, the servers whose bit changed go to an LDS
-// list, and the waves then visit the listed servers' index rows.
-template <bool CLEAR>
-__device__ __forceinline__ void walk_item(const RemedGraph& g, const HopIndex& ix,
-                                          const RemedSlice& sl, int beg, int n_inst,
-                                          uint32_t* list, unsigned* n_list, int& n_srv,
-                                          int3& fresh) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    for (int base = 0; base < n_inst; base += 256) {
-        if (threadIdx.x == 0) *n_list = 0;
-        __syncthreads();
-        if (base + (int)threadIdx.x < n_inst) {
-            const long long node = g.pkg_base + g.csr_pkgs[beg + base + threadIdx.x];
-            for (uint64_t e = g.rev_off[node]; e < g.rev_off[node + 1]; ++e) {
-                if (g.rev_et[e] != g.et_contains) continue;
-                const uint32_t r = g.rev_col[e] - ix.row_base;
-                if (r >= ix.num_rows) continue;  // not reached: see the preconditions
-                const uint32_t bit = 1u << (r & 31);
-                const uint32_t old = CLEAR ? atomicAnd(sl.srv + (r >> 5), ~bit)
-                                           : atomicOr(sl.srv + (r >> 5), bit);
-                if (((old & bit) != 0) != CLEAR) continue;  // another install had it
-                ++n_srv;
-                const unsigned slot = atomicAdd(n_list, 1u);
-                if (slot < REMED_T2_LIST) list[slot] = r;
-                else visit_row<CLEAR>(ix, sl, r, 0, 1, fresh);  // list full: alone
-            }
-        }
-        __syncthreads();
-        const unsigned n = *n_list < REMED_T2_LIST ? *n_list : REMED_T2_LIST;
-        for (unsigned j = wid; j < n; j += REMED_WAVES) visit_row<CLEAR>(ix, sl, list[j], lane, 64, fresh);
-        __syncthreads();
-    }
-}
+using RemedSlice = UnionSlice;
 
 // Tier 2: block b owns slice b of the pool and takes the queued items b,
 // b + gridDim.x, ...
@@ -374,8 +293,8 @@ __global__ void __launch_bounds__(256) remed_union_block_kernel(
         if (threadIdx.x < 4) totals[threadIdx.x] = 0;
         int n_srv = 0, unused_srv = 0;
         int3 fresh = make_int3(0, 0, 0), unused = make_int3(0, 0, 0);
-        walk_item<false>(g, ix, sl, beg, n_inst, list, &n_list, n_srv, fresh);
-        walk_item<true>(g, ix, sl, beg, n_inst, list, &n_list, unused_srv, unused);
+        walk_item<false, 3>(g, ix, sl, beg, n_inst, list, &n_list, n_srv, fresh);
+        walk_item<true, 3>(g, ix, sl, beg, n_inst, list, &n_list, unused_srv, unused);
         n_srv = wave_sum(n_srv);
         fresh.x = wave_sum(fresh.x);
         fresh.y = wave_sum(fresh.y);

@@ -211,6 +211,46 @@ _SIGNATURES = {
         _c, _c,                  # counters, host_counters
         _c, _c, _c, _c, _c,      # out_servers, out_agents, out_creds, out_tools, stream
     ], _i32),
+    "abom_toxic_cap": ([_i32], _i32),  # which
+    "abom_toxic_server_table": ([
+        _c, _c, _i64,          # reach_off, reach_col, num_rows
+        _c, _c, _i64, _i64,    # tool_caps, tool_is_db, tool_base, num_tools
+        _c, _c,                # table, stream
+    ], _i32),
+    "abom_toxic_fold": ([
+        _c, _c, _c, _c,        # pkg_idx, win_idx, scores, n_creds
+        _i64, _c, _i64, _i64,  # num_findings, vuln_of, num_windows, num_vulns
+        _c, _c, _c, _c,        # a_severity, a_kev, a_impact, tool_lut
+        _c, _c, _c, _i32,      # rev_off, rev_col, rev_et, et_contains
+        _i64, _c, _i64, _i64,  # pkg_base, table, row_base, num_rows
+        _c, _c, _c, _c, _c,    # state, matched, counters, host_counters, out_patterns
+        _c,                    # stream
+    ], _i32),
+    "abom_toxic_gather": ([
+        _c, _i64, _c,          # vulns, num_matched, state
+        _c, _c, _c, _c, _c,    # out_findings, out_packages, out_score, out_sev, out_kev
+        _c, _c,                # out_patterns, stream
+    ], _i32),
+    "abom_toxic_scatter": ([
+        _c, _c, _i64,          # pkg_idx, win_idx, num_findings
+        _c, _i64, _i64, _c,    # vuln_of, num_windows, num_vulns, state
+        _c, _i64, _i64, _c,    # vulns_off, num_matched, num_heads, csr_pkgs
+        _c,                    # stream
+    ], _i32),
+    "abom_toxic_union": ([
+        _i64, _c, _c, _i64,      # num_matched, vulns_off, csr_pkgs, pkg_base
+        _c, _c, _c, _i32,        # rev_off, rev_col, rev_et, et_contains
+        _c, _c, _i64, _i64,      # reach_off, reach_col, row_base, num_rows
+        _i64, _c, _c, _i64, _c,  # node_span, queue, pool, pool_slices, counters
+        _c, _c, _c,              # out_servers, out_agents, stream
+    ], _i32),
+    "abom_toxic_finish": ([
+        _c, _c, _c, _i64,      # pkg_idx, win_idx, scores, num_findings
+        _c, _i64, _i64,        # vuln_of, num_windows, num_vulns
+        _c, _i64, _c,          # vulns, num_matched, state
+        _c, _c, _c,            # v_agents, v_score, v_patterns
+        _c, _c, _c, _c, _c,    # patterns, combo_score, counters, host_counters, stream
+    ], _i32),
     "abom_path_relax": ([
         _c, _c, _c, _c,  # edge_src, col, etype, edge_weight
         _c, _c, _c, _c,  # cur, nxt, node_boost, etype_boost
@@ -1746,6 +1786,199 @@ def remediation_items_join(pkg_idx, win_idx, scores, item_of, arena: dict, rev: 
         nbr, pos = _hops_expand(torch, sbeg, cnt, ms >> 32, index["reach_col"])
         out[key] = count(torch.unique((pos << 32) | nbr) >> 32)
     return out
+
+
+# LDS caps of toxic_union_wave_kernel and the package count above which an
+# advisory goes straight to the bitmap tier (TOXIC_*, csrc/toxic.hip);
+# ``abom_toxic_cap`` reports the values the library was built with.
+TOXIC_SRV_CAP = 256
+TOXIC_AG_CAP = 256
+TOXIC_T1_PKGS = 1024
+# workspace tensors that are all-zero between calls
+TOXIC_ZERO_KEYS = ("toxic_state", "toxic_counters", "toxic_pool")
+_TOXIC_COUNTERS = 16
+_TOXIC_SHARED = 1 << 16  # server-table bit: the row has two or more agents
+
+
+def toxic_server_table(index: dict, tool_caps, tool_is_db, tool_base: int):
+    """The server table of csrc/toxic.hip: int32 [rows of ``index``], read as
+    u32 = caps_all | caps_db << 8 | shared << 16 -- the OR of ``tool_caps``
+    (uint8 [n_tools], indexed by node id - ``tool_base``) over the row's
+    tools, the same over its tools with ``tool_is_db`` set, and whether the
+    row has two or more agents.  Graph and caps only: it holds for as long as
+    the reach index and the caps tensor do."""
+    import torch
+
+    dev = index["reach_off"].device
+    if dev.type != "cuda":
+        raise ValueError(f"toxic_server_table: reach index on {dev}, expected a GPU tensor")
+    n_tools = tool_caps.numel()
+    _require(tool_caps, "tool_caps", torch.uint8, dev)
+    _require(tool_is_db, "tool_is_db", torch.uint8, dev, n_tools)
+    _require(index["reach_off"], "index.reach_off", torch.int32, dev)
+    _require(index["reach_col"], "index.reach_col", torch.int32, dev)
+    rows = index["reach_off"].shape[0]
+    table = torch.empty(rows, dtype=torch.int32, device=dev)
+    rc = load().abom_toxic_server_table(
+        _ptr(index["reach_off"]), _ptr(index["reach_col"]), rows,
+        _ptr(tool_caps), _ptr(tool_is_db), int(tool_base), n_tools, _ptr(table), _stream())
+    _check(rc, "abom_toxic_server_table")
+    return table
+
+
+def toxic_poison_servers(table, row_base: int):
+    """``poison_servers`` of ``cpu_ref.toxic_combinations`` from the server
+    table: ascending int32 node ids of the rows with two or more agents whose
+    unfiltered caps hold TC_WRITE and TC_READ or TC_RETRIEVAL."""
+    import torch
+
+    from agentbom_amd.ops.cpu_ref import TC_READ, TC_RETRIEVAL, TC_WRITE
+
+    hit = ((table & _TOXIC_SHARED) != 0) & ((table & TC_WRITE) != 0) \
+        & ((table & (TC_READ | TC_RETRIEVAL)) != 0)
+    return (torch.nonzero(hit).flatten() + int(row_base)).to(torch.int32)
+
+
+def _toxic_empty(torch, dev) -> dict:
+    from agentbom_amd.ops.cpu_ref import TOXIC_VULN_KEYS
+
+    dtypes = dict.fromkeys(TOXIC_VULN_KEYS, torch.int32)
+    dtypes.update(max_score=torch.float32, worst_sev=torch.uint8, kev=torch.uint8,
+                  patterns=torch.uint8)
+    return {k: torch.empty(0, dtype=dtypes[k], device=dev) for k in TOXIC_VULN_KEYS}
+
+
+def toxic_combinations(pkg_idx, win_idx, scores, n_creds, arena: dict, tool_lut, table,
+                       rev: dict, index: dict, et_contains: int, pkg_base: int,
+                       vuln_of=None, n_vulns: Optional[int] = None,
+                       workspace: Optional[dict] = None,
+                       pool_slices: Optional[int] = None) -> dict:
+    """Toxic combinations of the findings ``pkg_idx`` (int64, ascending),
+    ``win_idx`` (int64), ``scores`` (fp32, >= 0) and ``n_creds`` (int32) by
+    the kernels of csrc/toxic.hip; semantics: ``cpu_ref.toxic_combinations``.
+    ``table`` is :func:`toxic_server_table` of ``index``, the per-server reach
+    index, which must hold a row for every source of a CONTAINS edge;
+    ``arena`` gives ``severity``, ``kev`` and ``impact`` per window;
+    ``vuln_of`` int32 [W] maps a window to one of ``n_vulns`` advisories
+    (default: the identity; ``n_vulns`` is read from the device when not given).
+
+    Returns ``patterns`` uint8 [F] and ``combo_score`` fp32 [F]; ``vulns``,
+    the arrays of ``cpu_ref.TOXIC_VULN_KEYS`` per matched advisory, ascending;
+    and as host ints ``n_by_pattern`` (a list of six), ``n_multi_agent`` and
+    ``n_flagged``, the findings with a pattern.  Exact on the device: an
+    advisory too large for the LDS sets of the wave kernel is counted in a
+    slice of a bitmap pool of ``pool_slices`` slices (default: as many as fit
+    256 MiB, at most 256).
+
+    Two host reads: {matched advisories, (package, advisory) heads} after the
+    fold, to size the outputs, and the totals at the end, with {tier-2
+    advisories, pool rounds} left as ints in ``workspace["toxic_queued"]`` and
+    ``workspace["toxic_rounds"]``.  The workspace tensors named by
+    ``TOXIC_ZERO_KEYS`` are all-zero before and after a call."""
+    import torch
+
+    dev = pkg_idx.device
+    if dev.type != "cuda":
+        raise ValueError(f"toxic_combinations: pkg_idx on {dev}, expected a GPU tensor")
+    F = pkg_idx.numel()
+    W = arena["severity"].numel()
+    _require(pkg_idx, "pkg_idx", torch.int64, dev)
+    _require(win_idx, "win_idx", torch.int64, dev, F)
+    _require(scores, "scores", torch.float32, dev, F)
+    _require(n_creds, "n_creds", torch.int32, dev, F)
+    _require(arena["severity"], "arena.severity", torch.uint8, dev)
+    _require(arena["kev"], "arena.kev", torch.uint8, dev, W)
+    _require(arena["impact"], "arena.impact", torch.uint8, dev, W)
+    _require(tool_lut, "tool_lut", torch.uint8, dev, 9)
+    _require(rev["row_off"], "rev.row_off", torch.int64, dev)
+    _require(rev["col"], "rev.col", torch.int32, dev)
+    _require(rev["etype"], "rev.etype", torch.uint8, dev, rev["col"].numel())
+    _require(index["reach_off"], "index.reach_off", torch.int32, dev)
+    _require(index["reach_col"], "index.reach_col", torch.int32, dev)
+    rows = index["reach_off"].shape[0]
+    _require(table, "table", torch.int32, dev, rows)
+    if vuln_of is None:
+        V = W
+    else:
+        _require(vuln_of, "vuln_of", torch.int32, dev, W)
+        V = int(n_vulns) if n_vulns is not None else (int(vuln_of.max().item()) + 1 if W else 0)
+    ws = workspace if workspace is not None else {}
+    ws["toxic_queued"] = ws["toxic_rounds"] = 0
+    if F == 0:
+        return {"patterns": torch.empty(0, dtype=torch.uint8, device=dev),
+                "combo_score": torch.empty(0, dtype=torch.float32, device=dev),
+                "vulns": _toxic_empty(torch, dev), "n_by_pattern": [0] * 6,
+                "n_multi_agent": 0, "n_flagged": 0}
+    if F >= 1 << 31 or V >= 1 << 31:
+        raise RuntimeError(f"toxic_combinations: {F} findings / {V} advisories exceed int32")
+    lib = load()
+    span = _reach_node_span(index)
+    slice_words = (rows + 31) // 32 + (span + 31) // 32
+    if pool_slices is None:
+        pool_slices = max(1, min(_REMED_POOL_SLICES, _REMED_POOL_BYTES // (4 * slice_words)))
+    if pool_slices < 1:
+        raise ValueError("toxic_combinations: pool_slices < 1")
+    state = _buf(ws, "toxic_state", 8 * V, torch.int32, dev, zero=True)
+    counters = _buf(ws, "toxic_counters", _TOXIC_COUNTERS, torch.int32, dev, zero=True)
+    pool = _buf(ws, "toxic_pool", pool_slices * slice_words, torch.int32, dev, zero=True)
+    matched = _buf(ws, "toxic_matched", min(V, F), torch.int32, dev)
+    host = ws.get("toxic_host_counters")
+    if host is None:
+        host = ws["toxic_host_counters"] = torch.zeros(
+            _TOXIC_COUNTERS, dtype=torch.int32, pin_memory=True)
+    vuln_p = _ptr(vuln_of) if vuln_of is not None else None
+    patterns = torch.empty(F, dtype=torch.uint8, device=dev)
+    combo = torch.empty(F, dtype=torch.float32, device=dev)
+    rc = lib.abom_toxic_fold(
+        _ptr(pkg_idx), _ptr(win_idx), _ptr(scores), _ptr(n_creds), F, vuln_p, W, V,
+        _ptr(arena["severity"]), _ptr(arena["kev"]), _ptr(arena["impact"]), _ptr(tool_lut),
+        _ptr(rev["row_off"]), _ptr(rev["col"]), _ptr(rev["etype"]), int(et_contains),
+        int(pkg_base), _ptr(table), int(index["row_base"]), rows,
+        _ptr(state), _ptr(matched), _ptr(counters), _ptr(host), _ptr(patterns), _stream())
+    _check(rc, "abom_toxic_fold")
+    done = torch.cuda.Event()
+    done.record()
+    done.synchronize()  # the host read that sizes the outputs
+    M, _, _, NH = host[:4].tolist()
+    vulns = torch.sort(matched[:M]).values
+    i32 = {k: torch.empty(M, dtype=torch.int32, device=dev)
+           for k in ("n_findings", "n_packages", "n_servers", "n_agents", "max_score")}
+    u8 = {k: torch.empty(M, dtype=torch.uint8, device=dev)
+          for k in ("worst_sev", "kev", "patterns")}
+    rc = lib.abom_toxic_gather(
+        _ptr(vulns), M, _ptr(state), _ptr(i32["n_findings"]), _ptr(i32["n_packages"]),
+        _ptr(i32["max_score"]), _ptr(u8["worst_sev"]), _ptr(u8["kev"]), _ptr(u8["patterns"]),
+        _stream())
+    _check(rc, "abom_toxic_gather")
+    # advisory -> its distinct matched packages as a CSR; order within one is free
+    vulns_off = torch.zeros(M + 1, dtype=torch.int32, device=dev)
+    torch.cumsum(i32["n_packages"], 0, out=vulns_off[1:])
+    csr_pkgs = torch.empty(NH, dtype=torch.int32, device=dev)
+    rc = lib.abom_toxic_scatter(
+        _ptr(pkg_idx), _ptr(win_idx), F, vuln_p, W, V, _ptr(state), _ptr(vulns_off), M, NH,
+        _ptr(csr_pkgs), _stream())
+    _check(rc, "abom_toxic_scatter")
+    queue = _buf(ws, "toxic_queue", M, torch.int32, dev)
+    rc = lib.abom_toxic_union(
+        M, _ptr(vulns_off), _ptr(csr_pkgs), int(pkg_base),
+        _ptr(rev["row_off"]), _ptr(rev["col"]), _ptr(rev["etype"]), int(et_contains),
+        _ptr(index["reach_off"]), _ptr(index["reach_col"]), int(index["row_base"]), rows,
+        span, _ptr(queue), _ptr(pool), int(pool_slices), _ptr(counters),
+        _ptr(i32["n_servers"]), _ptr(i32["n_agents"]), _stream())
+    _check(rc, "abom_toxic_union")
+    rc = lib.abom_toxic_finish(
+        _ptr(pkg_idx), _ptr(win_idx), _ptr(scores), F, vuln_p, W, V, _ptr(vulns), M,
+        _ptr(state), _ptr(i32["n_agents"]), _ptr(i32["max_score"]), _ptr(u8["patterns"]),
+        _ptr(patterns), _ptr(combo), _ptr(counters), _ptr(host), _stream())
+    _check(rc, "abom_toxic_finish")
+    done.record()
+    done.synchronize()
+    totals = host.tolist()
+    ws["toxic_queued"], ws["toxic_rounds"] = totals[1], totals[2]
+    per = {"vuln": vulns, **i32, **u8}
+    per["max_score"] = per["max_score"].view(torch.float32)
+    return {"patterns": patterns, "combo_score": combo, "vulns": per,
+            "n_by_pattern": totals[4:10], "n_multi_agent": totals[10], "n_flagged": totals[11]}
 
 
 def risk_weights_array() -> np.ndarray:
