@@ -20,6 +20,21 @@ struct HopIndex {
     uint32_t num_agents;
 };
 
+// host: the agent fields are null / 0 for a user of the server rows alone
+inline HopIndex make_hop_index(const void* reach_off, const void* reach_col, long long row_base,
+                               long long num_rows, const void* agent_off, const void* agent_srv,
+                               long long num_agents) {
+    HopIndex ix;
+    ix.reach_off = (const int4*)reach_off;
+    ix.reach_col = (const uint32_t*)reach_col;
+    ix.row_base = (uint32_t)row_base;
+    ix.num_rows = (uint32_t)num_rows;
+    ix.agent_off = (const int*)agent_off;
+    ix.agent_srv = (const uint32_t*)agent_srv;
+    ix.num_agents = (uint32_t)num_agents;
+    return ix;
+}
+
 enum HopSegment { AGENTS_OF_SERVER, CREDS_OF_SERVER, TOOLS_OF_SERVER, SERVERS_OF_AGENT };
 
 // (begin, length) of the node's segment; empty for a node without a row

@@ -47,7 +47,7 @@ constexpr int HOPS_MAX_DEPTH = 5;
 constexpr int HOPS_FAST_BUDGET = 64;
 constexpr int HOPS_FAST_ROW = 8;
 
-// HopIndex, hop_segment, append_distinct and expand_append: abom_sets.h
+// HopIndex, make_hop_index, hop_segment, append_distinct, expand_append: abom_sets.h
 
 __device__ __forceinline__ void write_hops(
     int* __restrict__ out_hops, int* __restrict__ out_creds, uint8_t* __restrict__ out_depth,
@@ -269,20 +269,6 @@ static int launch_blast_hops(
                        (int*)out_hop_agents, (int*)out_creds,
                        (uint8_t*)out_depth, (uint8_t*)out_overflow);
     return (int)hipGetLastError();
-}
-
-static HopIndex make_hop_index(const void* reach_off, const void* reach_col, long long row_base,
-                               long long num_rows, const void* agent_off, const void* agent_srv,
-                               long long num_agents) {
-    HopIndex ix;
-    ix.reach_off = (const int4*)reach_off;
-    ix.reach_col = (const uint32_t*)reach_col;
-    ix.row_base = (uint32_t)row_base;
-    ix.num_rows = (uint32_t)num_rows;
-    ix.agent_off = (const int*)agent_off;
-    ix.agent_srv = (const uint32_t*)agent_srv;
-    ix.num_agents = (uint32_t)num_agents;
-    return ix;
 }
 
 }  // namespace abom

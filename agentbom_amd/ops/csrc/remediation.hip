@@ -22,18 +22,10 @@
 //   position + 1 stays for the scatter.
 // abom_remediation_scatter  one thread per finding; the head of a package run
 //   claims a place in its item's span of `csr_pkgs` through the cursor.
-// abom_remediation_union    tier 1, one wave per matched item: distinct
-//   servers, agents, creds and tools as capped LDS sets (abom_sets.h).  An
-//   item past a cap, or with more than REMED_T1_INSTALLS installs, goes to
-//   the tier-2 queue.  Tier 2, one block per slice of the bitmap pool: a
-//   slice holds one bit per reach-index row and three planes of one bit per
-//   node id below `node_span`; atomicOr sets a bit and the old word says
-//   whether it was new.  A block walks its item twice, the second time
-//   clearing what the first set, so a slice is all-zero whenever a block
-//   leaves an item, and block b takes the queued items b, b + slices, ...
-//   The set walks of both tiers live in abom_union.h, shared with toxic.hip.
-//   Tier 1 also returns slot and cursor to 0: `state`, `pool` and `counters`
-//   are all-zero on return.
+// abom_remediation_union    the two union tiers of abom_union.h (shared with
+//   toxic.hip) with three planes: distinct servers, agents, creds and tools
+//   per matched item.  Tier 1 also returns slot and cursor to 0: `state`,
+//   `pool` and `counters` are all-zero on return.
 //
 // Preconditions, as EstateEngine.step and build_reach_index give them:
 // pkg_idx ascending; the installs of one item carry the same windows; every
@@ -54,15 +46,21 @@ constexpr int REMED_SRV_CAP = 256;
 constexpr int REMED_AG_CAP = 256;
 constexpr int REMED_CR_CAP = 256;
 constexpr int REMED_TL_CAP = 512;
-constexpr int REMED_WAVES = UNION_WAVES;
 // an item with more installs than this skips tier 1: on an estate that
 // spreads installs over its servers it would pass the server cap anyway
 constexpr int REMED_T1_INSTALLS = 4 * REMED_SRV_CAP;
-constexpr int REMED_T2_LIST = UNION_T2_LIST;
-constexpr int REMED_ROW = 8;  // u32 words per item of `state`
 
-enum RemedWord { RW_FINDINGS, RW_INSTALLS, RW_SCORE, RW_SEV, RW_KEV, RW_HEAD, RW_SLOT, RW_CURSOR };
-enum RemedCounter { RC_MATCHED, RC_QUEUED, RC_ROUNDS, RC_INSTALLS };
+struct RemedUnion {
+    static constexpr int SRV_CAP = REMED_SRV_CAP, AG_CAP = REMED_AG_CAP;
+    static constexpr int CR_CAP = REMED_CR_CAP, TL_CAP = REMED_TL_CAP;
+    static constexpr int PLANES = 3, T1_INSTALLS = REMED_T1_INSTALLS;
+    static constexpr bool ZERO_SLOT = true;
+};
+
+enum RemedWord { RW_FINDINGS, RW_INSTALLS, RW_SCORE, RW_SEV, RW_KEV, RW_HEAD,
+                 RW_SLOT = UW_SLOT, RW_CURSOR = UW_CURSOR };
+enum RemedCounter { RC_MATCHED, RC_QUEUED = UC_QUEUED, RC_ROUNDS = UC_ROUNDS, RC_INSTALLS };
+static_assert(RW_HEAD < RW_SLOT && RC_MATCHED < RC_QUEUED && RC_ROUNDS < RC_INSTALLS);
 
 __global__ void __launch_bounds__(256) remed_fold_kernel(
     const long long* __restrict__ pkg_idx, const long long* __restrict__ win_idx,
@@ -110,7 +108,7 @@ __global__ void __launch_bounds__(256) remed_fold_kernel(
         }
         bool fresh = false;
         if (first) {
-            uint32_t* row = state + (size_t)item * REMED_ROW;
+            uint32_t* row = state + (size_t)item * UNION_ROW;
             const unsigned long long below_end = end >= 64 ? ~0ull : (1ull << end) - 1;
             const unsigned long long run_heads = heads & below_end & ~((1ull << lane) - 1);
             fresh = atomicAdd(&row[RW_FINDINGS], (uint32_t)(end - lane)) == 0;
@@ -138,10 +136,10 @@ __global__ void __launch_bounds__(256) remed_gather_kernel(
     int* __restrict__ out_vulns, uint32_t* __restrict__ out_score, uint8_t* __restrict__ out_sev,
     uint8_t* __restrict__ out_kev, long long* __restrict__ out_fix_hi,
     long long* __restrict__ out_fix_lo, int* __restrict__ out_unfixed) {
-    const WaveId w = wave_id(REMED_WAVES);
+    const WaveId w = wave_id(UNION_WAVES);
     const int lane = w.lane;
     for (long long m = w.wave; m < M; m += w.n_waves) {
-        uint32_t* row = state + (size_t)items[m] * REMED_ROW;
+        uint32_t* row = state + (size_t)items[m] * UNION_ROW;
         const uint32_t n_find = row[RW_FINDINGS], n_inst = row[RW_INSTALLS];
         const uint32_t score = row[RW_SCORE], sev = row[RW_SEV], kev = row[RW_KEV];
         // a matched item has a head finding, so 1 <= row[RW_HEAD] <= F
@@ -191,7 +189,7 @@ __global__ void __launch_bounds__(256) remed_gather_kernel(
             out_unfixed[m] = n_unfixed;
             row[RW_FINDINGS] = 0; row[RW_INSTALLS] = 0; row[RW_SCORE] = 0;
             row[RW_SEV] = 0; row[RW_KEV] = 0; row[RW_HEAD] = 0;
-            row[RW_SLOT] = (uint32_t)m + 1;
+            slot_set(row, m);
         }
     }
 }
@@ -204,115 +202,8 @@ __global__ void __launch_bounds__(256) remed_scatter_kernel(
     for (long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += stride) {
         const long long pkg = pkg_idx[f];
         if (f != 0 && pkg_idx[f - 1] == pkg) continue;
-        uint32_t* row = state + (size_t)(uint32_t)item_of[pkg] * REMED_ROW;
-        const long long m = (long long)row[RW_SLOT] - 1;
-        if (m < 0 || m >= M) continue;  // not reached with the gather's slots
-        const long long at = (long long)items_off[m] + atomicAdd(&row[RW_CURSOR], 1u);
-        if (at < n_installs) csr_pkgs[at] = (int)pkg;
-    }
-}
-
-using RemedGraph = UnionGraph;
-
-// Tier 1: one wave per matched item.
-__global__ void __launch_bounds__(256) remed_union_wave_kernel(
-    const int* __restrict__ items, long long M, RemedGraph g, HopIndex ix,
-    uint32_t* __restrict__ state, uint32_t* __restrict__ queue,
-    unsigned int* __restrict__ counters,
-    int* __restrict__ out_servers, int* __restrict__ out_agents, int* __restrict__ out_creds,
-    int* __restrict__ out_tools) {
-    __shared__ uint32_t lds_srv[REMED_WAVES][REMED_SRV_CAP];
-    __shared__ uint32_t lds_ag[REMED_WAVES][REMED_AG_CAP];
-    __shared__ uint32_t lds_cr[REMED_WAVES][REMED_CR_CAP];
-    __shared__ uint32_t lds_tl[REMED_WAVES][REMED_TL_CAP];
-    __shared__ uint32_t lds_stage[REMED_WAVES][64];
-    __shared__ int lds_beg[REMED_WAVES][64];
-    __shared__ int lds_pref[REMED_WAVES][64];
-
-    const WaveId w = wave_id(REMED_WAVES);
-    const int lane = w.lane, wid = w.wid;
-    uint32_t* srv = lds_srv[wid];
-    uint32_t* stage = lds_stage[wid];
-    int* t_beg = lds_beg[wid];
-    int* t_pref = lds_pref[wid];
-
-    for (long long m = w.wave; m < M; m += w.n_waves) {
-        if (lane == 0) {
-            uint32_t* row = state + (size_t)items[m] * REMED_ROW;
-            row[RW_SLOT] = 0;
-            row[RW_CURSOR] = 0;
-        }
-        const int beg = g.items_off[m];
-        const int n_inst = g.items_off[m + 1] - beg;
-        int n_srv = 0, n_ag = 0, n_cr = 0, n_tl = 0;
-        bool ok = n_inst <= REMED_T1_INSTALLS;
-        // the distinct sources of CONTAINS edges into the installs
-        ok = ok && collect_servers(g, beg, n_inst, srv, n_srv, REMED_SRV_CAP, stage, lane);
-        ok = ok && expand_append<AGENTS_OF_SERVER>(ix, srv, 0, n_srv, lds_ag[wid], n_ag,
-                                                  REMED_AG_CAP, t_beg, t_pref, stage, lane);
-        ok = ok && expand_append<CREDS_OF_SERVER>(ix, srv, 0, n_srv, lds_cr[wid], n_cr,
-                                                 REMED_CR_CAP, t_beg, t_pref, stage, lane);
-        ok = ok && expand_append<TOOLS_OF_SERVER>(ix, srv, 0, n_srv, lds_tl[wid], n_tl,
-                                                 REMED_TL_CAP, t_beg, t_pref, stage, lane);
-        if (ok && lane == 0) {
-            out_servers[m] = n_srv;
-            out_agents[m] = n_ag;
-            out_creds[m] = n_cr;
-            out_tools[m] = n_tl;
-        }
-        wave_queue_push(!ok && lane == 0, (uint32_t)m, queue, &counters[RC_QUEUED], lane);
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-using RemedSlice = UnionSlice;
-
-// Tier 2: block b owns slice b of the pool and takes the queued items b,
-// b + gridDim.x, ...
-__global__ void __launch_bounds__(256) remed_union_block_kernel(
-    RemedGraph g, HopIndex ix, const uint32_t* __restrict__ queue,
-    unsigned int* __restrict__ counters, uint32_t* __restrict__ pool,
-    long long srv_words, long long plane_words, uint32_t node_span,
-    int* __restrict__ out_servers, int* __restrict__ out_agents, int* __restrict__ out_creds,
-    int* __restrict__ out_tools) {
-    __shared__ uint32_t list[REMED_T2_LIST];
-    __shared__ unsigned n_list;
-    __shared__ int totals[4];
-    const unsigned n_queued = counters[RC_QUEUED];
-    RemedSlice sl;
-    sl.srv = pool + (size_t)blockIdx.x * (size_t)(srv_words + 3 * plane_words);
-    sl.planes = sl.srv + srv_words;
-    sl.plane_words = plane_words;
-    sl.node_span = node_span;
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        counters[RC_ROUNDS] = (n_queued + gridDim.x - 1) / gridDim.x;
-    for (unsigned q = blockIdx.x; q < n_queued; q += gridDim.x) {
-        const long long m = queue[q];
-        const int beg = g.items_off[m];
-        const int n_inst = g.items_off[m + 1] - beg;
-        if (threadIdx.x < 4) totals[threadIdx.x] = 0;
-        int n_srv = 0, unused_srv = 0;
-        int3 fresh = make_int3(0, 0, 0), unused = make_int3(0, 0, 0);
-        walk_item<false, 3>(g, ix, sl, beg, n_inst, list, &n_list, n_srv, fresh);
-        walk_item<true, 3>(g, ix, sl, beg, n_inst, list, &n_list, unused_srv, unused);
-        n_srv = wave_sum(n_srv);
-        fresh.x = wave_sum(fresh.x);
-        fresh.y = wave_sum(fresh.y);
-        fresh.z = wave_sum(fresh.z);
-        if ((threadIdx.x & 63) == 0) {
-            atomicAdd(&totals[0], n_srv);
-            atomicAdd(&totals[1], fresh.x);
-            atomicAdd(&totals[2], fresh.y);
-            atomicAdd(&totals[3], fresh.z);
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            out_servers[m] = totals[0];
-            out_agents[m] = totals[1];
-            out_creds[m] = totals[2];
-            out_tools[m] = totals[3];
-        }
-        __syncthreads();
+        uint32_t* row = state + (size_t)(uint32_t)item_of[pkg] * UNION_ROW;
+        slot_claim(row, items_off, M, n_installs, csr_pkgs, (int)pkg);
     }
 }
 
@@ -359,7 +250,7 @@ extern "C" int abom_remediation_gather(
     void* out_unfixed, void* stream) {
     if (num_items <= 0) return 0;
     hipLaunchKernelGGL(abom::remed_gather_kernel,
-                       dim3(abom::grid_for(num_items, abom::REMED_WAVES)), dim3(256), 0,
+                       dim3(abom::grid_for(num_items, abom::UNION_WAVES)), dim3(256), 0,
                        (hipStream_t)stream,
                        (const int*)items, num_items, (const long long*)pkg_idx,
                        (const long long*)win_idx, num_findings, (const uint8_t*)w_flags,
@@ -396,40 +287,13 @@ extern "C" int abom_remediation_union(
     void* counters, void* host_counters,
     void* out_servers, void* out_agents, void* out_creds, void* out_tools, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (pool_slices < 1 || node_span < 0 || node_span >= (1ll << 32)) return (int)hipErrorInvalidValue;
-    if (num_items > 0) {
-        abom::RemedGraph g;
-        g.rev_off = (const uint64_t*)rev_off;
-        g.rev_col = (const uint32_t*)rev_col;
-        g.rev_et = (const uint8_t*)rev_et;
-        g.et_contains = (uint8_t)et_contains;
-        g.pkg_base = pkg_base;
-        g.items_off = (const int*)items_off;
-        g.csr_pkgs = (const int*)csr_pkgs;
-        abom::HopIndex ix;
-        ix.reach_off = (const int4*)reach_off;
-        ix.reach_col = (const uint32_t*)reach_col;
-        ix.row_base = (uint32_t)row_base;
-        ix.num_rows = (uint32_t)num_rows;
-        ix.agent_off = nullptr;
-        ix.agent_srv = nullptr;
-        ix.num_agents = 0;
-        hipLaunchKernelGGL(abom::remed_union_wave_kernel,
-                           dim3(abom::grid_for(num_items, abom::REMED_WAVES)), dim3(256), 0, s,
-                           (const int*)items, num_items, g, ix, (uint32_t*)state,
-                           (uint32_t*)queue, (unsigned int*)counters,
-                           (int*)out_servers, (int*)out_agents, (int*)out_creds, (int*)out_tools);
-        ABOM_CHECK(hipGetLastError());
-        // the queue length is known on the device only: one block per slice,
-        // a block without a queued item leaves at once
-        const long long blocks = pool_slices < num_items ? pool_slices : num_items;
-        hipLaunchKernelGGL(abom::remed_union_block_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
-                           g, ix, (const uint32_t*)queue, (unsigned int*)counters,
-                           (uint32_t*)pool, (num_rows + 31) / 32, (node_span + 31) / 32,
-                           (uint32_t)node_span,
-                           (int*)out_servers, (int*)out_agents, (int*)out_creds, (int*)out_tools);
-        ABOM_CHECK(hipGetLastError());
-    }
+    const abom::UnionOut out = {{(int*)out_servers, (int*)out_agents, (int*)out_creds,
+                                 (int*)out_tools}};
+    const int rc = abom::launch_union_tiers<abom::RemedUnion>(
+        items, num_items, items_off, csr_pkgs, pkg_base, rev_off, rev_col, rev_et, et_contains,
+        reach_off, reach_col, row_base, num_rows, node_span, state, queue, pool, pool_slices,
+        counters, out, s);
+    if (rc != 0) return rc;
     ABOM_CHECK(hipMemcpyAsync(host_counters, counters, 4 * sizeof(unsigned int),
                               hipMemcpyDeviceToHost, s));
     ABOM_CHECK(hipMemsetAsync(counters, 0, 4 * sizeof(unsigned int), s));

@@ -27,10 +27,9 @@
 //   fields move to the outputs, their words return to 0, slot = position + 1.
 // abom_toxic_scatter  one thread per finding; a (package, advisory) head
 //   claims a place in its advisory's span of `csr_pkgs` through the cursor.
-// abom_toxic_union    distinct servers, then distinct agents per matched
-//   advisory: tier 1 one wave per advisory with capped LDS sets, tier 2 one
-//   block per slice of a bitmap pool for an advisory past a cap or with more
-//   than TOXIC_T1_PKGS packages (abom_union.h, shared with remediation.hip).
+// abom_toxic_union    the two union tiers of abom_union.h (shared with
+//   remediation.hip) with one plane: distinct servers and agents per matched
+//   advisory.  Tier 1 leaves the slot for the finish.
 // abom_toxic_finish   one thread per finding: the multi-agent bit from the
 //   advisory's agents, combo_score, and the histogram, reduced in the wave
 //   over the thread's whole stride before the atomics; then one thread per
@@ -56,8 +55,13 @@ constexpr int TOXIC_SRV_CAP = 256;
 constexpr int TOXIC_AG_CAP = 256;
 // an advisory with more packages than this skips tier 1
 constexpr int TOXIC_T1_PKGS = 4 * TOXIC_SRV_CAP;
-constexpr int TOXIC_ROW = 8;  // u32 words per advisory of `state`
 constexpr int TOXIC_COUNTERS = 16;
+
+struct ToxicUnion {
+    static constexpr int SRV_CAP = TOXIC_SRV_CAP, AG_CAP = TOXIC_AG_CAP;
+    static constexpr int PLANES = 1, T1_INSTALLS = TOXIC_T1_PKGS;
+    static constexpr bool ZERO_SLOT = false;  // toxic_finish_kernel reads the slot
+};
 
 // mirrors of cpu_ref.TC_* and cpu_ref.TP_*
 constexpr uint32_t TC_EXEC = 1, TC_WRITE = 2, TC_DELETE = 4, TC_RETRIEVAL = 16;
@@ -67,9 +71,11 @@ constexpr uint32_t TP_CACHE_POISON = 8, TP_LATERAL_CHAIN = 16, TP_MULTI_AGENT_CV
 constexpr uint32_t TOXIC_HOT_SEVERITY = 4;
 constexpr int TOXIC_MULTI_AGENTS = 3;
 
-enum ToxicWord { TW_FINDINGS, TW_PKGS, TW_SCORE, TW_SEV, TW_KEV, TW_PAT, TW_SLOT, TW_CURSOR };
-enum ToxicCounter { XC_MATCHED, XC_QUEUED, XC_ROUNDS, XC_HEADS, XC_HIST, XC_MULTI = XC_HIST + 6,
-                    XC_ANY };
+enum ToxicWord { TW_FINDINGS, TW_PKGS, TW_SCORE, TW_SEV, TW_KEV, TW_PAT,
+                 TW_SLOT = UW_SLOT, TW_CURSOR = UW_CURSOR };
+enum ToxicCounter { XC_MATCHED, XC_QUEUED = UC_QUEUED, XC_ROUNDS = UC_ROUNDS, XC_HEADS, XC_HIST,
+                    XC_MULTI = XC_HIST + 6, XC_ANY };
+static_assert(TW_PAT < TW_SLOT && XC_MATCHED < XC_QUEUED && XC_ROUNDS < XC_HEADS);
 
 __global__ void __launch_bounds__(256) toxic_server_table_kernel(
     const int4* __restrict__ reach_off, const uint32_t* __restrict__ reach_col, long long num_rows,
@@ -162,7 +168,7 @@ __global__ void __launch_bounds__(256) toxic_fold_kernel(
             if (hot && (exposed & TC_RETRIEVAL)) bits |= TP_CACHE_POISON;
             if (hot && (word >> 16 & 1u)) bits |= TP_LATERAL_CHAIN;
             head = toxic_head(fs, f, pkg, v);
-            uint32_t* row = state + (size_t)v * TOXIC_ROW;
+            uint32_t* row = state + (size_t)v * UNION_ROW;
             fresh = atomicAdd(&row[TW_FINDINGS], 1u) == 0;
             if (head) atomicAdd(&row[TW_PKGS], 1u);
             // scores are >= 0: the order of the bit patterns is the order of the values
@@ -185,7 +191,7 @@ __global__ void __launch_bounds__(256) toxic_gather_kernel(
     uint8_t* __restrict__ out_patterns) {
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += stride) {
-        uint32_t* row = state + (size_t)vulns[m] * TOXIC_ROW;
+        uint32_t* row = state + (size_t)vulns[m] * UNION_ROW;
         out_findings[m] = (int)row[TW_FINDINGS];
         out_packages[m] = (int)row[TW_PKGS];
         out_score[m] = row[TW_SCORE];
@@ -194,7 +200,7 @@ __global__ void __launch_bounds__(256) toxic_gather_kernel(
         out_patterns[m] = (uint8_t)row[TW_PAT];
         row[TW_FINDINGS] = 0; row[TW_PKGS] = 0; row[TW_SCORE] = 0;
         row[TW_SEV] = 0; row[TW_KEV] = 0; row[TW_PAT] = 0;
-        row[TW_SLOT] = (uint32_t)m + 1;
+        slot_set(row, m);
     }
 }
 
@@ -207,86 +213,8 @@ __global__ void __launch_bounds__(256) toxic_scatter_kernel(
         if (v < 0) continue;
         const long long pkg = fs.pkg_idx[f];
         if (!toxic_head(fs, f, pkg, v)) continue;
-        uint32_t* row = state + (size_t)v * TOXIC_ROW;
-        const long long m = (long long)row[TW_SLOT] - 1;
-        if (m < 0 || m >= M) continue;  // not reached with the gather's slots
-        const long long at = (long long)vulns_off[m] + atomicAdd(&row[TW_CURSOR], 1u);
-        if (at < n_heads) csr_pkgs[at] = (int)pkg;
-    }
-}
-
-// Tier 1: one wave per matched advisory.
-__global__ void __launch_bounds__(256) toxic_union_wave_kernel(
-    long long M, UnionGraph g, HopIndex ix, uint32_t* __restrict__ queue,
-    unsigned int* __restrict__ counters, int* __restrict__ out_servers,
-    int* __restrict__ out_agents) {
-    __shared__ uint32_t lds_srv[UNION_WAVES][TOXIC_SRV_CAP];
-    __shared__ uint32_t lds_ag[UNION_WAVES][TOXIC_AG_CAP];
-    __shared__ uint32_t lds_stage[UNION_WAVES][64];
-    __shared__ int lds_beg[UNION_WAVES][64];
-    __shared__ int lds_pref[UNION_WAVES][64];
-
-    const WaveId w = wave_id(UNION_WAVES);
-    const int lane = w.lane, wid = w.wid;
-    for (long long m = w.wave; m < M; m += w.n_waves) {
-        const int beg = g.items_off[m];
-        const int n_pkgs = g.items_off[m + 1] - beg;
-        int n_srv = 0, n_ag = 0;
-        bool ok = n_pkgs <= TOXIC_T1_PKGS;
-        ok = ok && collect_servers(g, beg, n_pkgs, lds_srv[wid], n_srv, TOXIC_SRV_CAP,
-                                   lds_stage[wid], lane);
-        ok = ok && expand_append<AGENTS_OF_SERVER>(ix, lds_srv[wid], 0, n_srv, lds_ag[wid], n_ag,
-                                                  TOXIC_AG_CAP, lds_beg[wid], lds_pref[wid],
-                                                  lds_stage[wid], lane);
-        if (ok && lane == 0) {
-            out_servers[m] = n_srv;
-            out_agents[m] = n_ag;
-        }
-        wave_queue_push(!ok && lane == 0, (uint32_t)m, queue, &counters[XC_QUEUED], lane);
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-// Tier 2: block b owns slice b of the pool (one bit per reach-index row, one
-// plane of one bit per node id for the agents) and takes the queued
-// advisories b, b + gridDim.x, ...
-__global__ void __launch_bounds__(256) toxic_union_block_kernel(
-    UnionGraph g, HopIndex ix, const uint32_t* __restrict__ queue,
-    unsigned int* __restrict__ counters, uint32_t* __restrict__ pool,
-    long long srv_words, long long plane_words, uint32_t node_span,
-    int* __restrict__ out_servers, int* __restrict__ out_agents) {
-    __shared__ uint32_t list[UNION_T2_LIST];
-    __shared__ unsigned n_list;
-    __shared__ int totals[2];
-    const unsigned n_queued = counters[XC_QUEUED];
-    UnionSlice sl;
-    sl.srv = pool + (size_t)blockIdx.x * (size_t)(srv_words + plane_words);
-    sl.planes = sl.srv + srv_words;
-    sl.plane_words = plane_words;
-    sl.node_span = node_span;
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        counters[XC_ROUNDS] = (n_queued + gridDim.x - 1) / gridDim.x;
-    for (unsigned q = blockIdx.x; q < n_queued; q += gridDim.x) {
-        const long long m = queue[q];
-        const int beg = g.items_off[m];
-        const int n_pkgs = g.items_off[m + 1] - beg;
-        if (threadIdx.x < 2) totals[threadIdx.x] = 0;
-        int n_srv = 0, unused_srv = 0;
-        int3 fresh = make_int3(0, 0, 0), unused = make_int3(0, 0, 0);
-        walk_item<false, 1>(g, ix, sl, beg, n_pkgs, list, &n_list, n_srv, fresh);
-        walk_item<true, 1>(g, ix, sl, beg, n_pkgs, list, &n_list, unused_srv, unused);
-        n_srv = wave_sum(n_srv);
-        fresh.x = wave_sum(fresh.x);
-        if ((threadIdx.x & 63) == 0) {
-            atomicAdd(&totals[0], n_srv);
-            atomicAdd(&totals[1], fresh.x);
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            out_servers[m] = totals[0];
-            out_agents[m] = totals[1];
-        }
-        __syncthreads();
+        uint32_t* row = state + (size_t)v * UNION_ROW;
+        slot_claim(row, vulns_off, M, n_heads, csr_pkgs, (int)pkg);
     }
 }
 
@@ -313,8 +241,9 @@ __global__ void __launch_bounds__(256) toxic_finish_kernel(
             float m_score = 0.0f;
             const long long v = toxic_vuln(fs, f);
             if (v >= 0) {
-                const long long m = (long long)state[(size_t)v * TOXIC_ROW + TW_SLOT] - 1;
-                if (m >= 0 && m < M && v_agents[m] >= TOXIC_MULTI_AGENTS) {
+                long long m;
+                if (slot_get(state + (size_t)v * UNION_ROW, M, m) &&
+                    v_agents[m] >= TOXIC_MULTI_AGENTS) {
                     bits |= TP_MULTI_AGENT_CVE;
                     m_score = __uint_as_float(v_score[m]);
                 }
@@ -351,9 +280,8 @@ __global__ void __launch_bounds__(256) toxic_close_kernel(
         const long long m = base + lane;
         bool multi = false;
         if (m < M) {
-            uint32_t* row = state + (size_t)vulns[m] * TOXIC_ROW;
-            row[TW_SLOT] = 0;
-            row[TW_CURSOR] = 0;
+            uint32_t* row = state + (size_t)vulns[m] * UNION_ROW;
+            slot_clear(row);
             multi = v_agents[m] >= TOXIC_MULTI_AGENTS;
             if (multi) v_patterns[m] |= (uint8_t)TP_MULTI_AGENT_CVE;
         }
@@ -465,38 +393,12 @@ extern "C" int abom_toxic_union(
     const void* reach_off, const void* reach_col, long long row_base, long long num_rows,
     long long node_span, void* queue, void* pool, long long pool_slices, void* counters,
     void* out_servers, void* out_agents, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (pool_slices < 1 || node_span < 0 || node_span >= (1ll << 32)) return (int)hipErrorInvalidValue;
-    if (num_matched <= 0) return 0;
-    abom::UnionGraph g;
-    g.rev_off = (const uint64_t*)rev_off;
-    g.rev_col = (const uint32_t*)rev_col;
-    g.rev_et = (const uint8_t*)rev_et;
-    g.et_contains = (uint8_t)et_contains;
-    g.pkg_base = pkg_base;
-    g.items_off = (const int*)vulns_off;
-    g.csr_pkgs = (const int*)csr_pkgs;
-    abom::HopIndex ix;
-    ix.reach_off = (const int4*)reach_off;
-    ix.reach_col = (const uint32_t*)reach_col;
-    ix.row_base = (uint32_t)row_base;
-    ix.num_rows = (uint32_t)num_rows;
-    ix.agent_off = nullptr;
-    ix.agent_srv = nullptr;
-    ix.num_agents = 0;
-    hipLaunchKernelGGL(abom::toxic_union_wave_kernel,
-                       dim3(abom::grid_for(num_matched, abom::UNION_WAVES)), dim3(256), 0, s,
-                       num_matched, g, ix, (uint32_t*)queue, (unsigned int*)counters,
-                       (int*)out_servers, (int*)out_agents);
-    ABOM_CHECK(hipGetLastError());
-    // the queue length is known on the device only: one block per slice, a
-    // block without a queued advisory leaves at once
-    const long long blocks = pool_slices < num_matched ? pool_slices : num_matched;
-    hipLaunchKernelGGL(abom::toxic_union_block_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
-                       g, ix, (const uint32_t*)queue, (unsigned int*)counters, (uint32_t*)pool,
-                       (num_rows + 31) / 32, (node_span + 31) / 32, (uint32_t)node_span,
-                       (int*)out_servers, (int*)out_agents);
-    return (int)hipGetLastError();
+    const abom::UnionOut out = {{(int*)out_servers, (int*)out_agents, nullptr, nullptr}};
+    // tier 1 leaves the slots alone: no items, no state
+    return abom::launch_union_tiers<abom::ToxicUnion>(
+        nullptr, num_matched, vulns_off, csr_pkgs, pkg_base, rev_off, rev_col, rev_et,
+        et_contains, reach_off, reach_col, row_base, num_rows, node_span, nullptr, queue, pool,
+        pool_slices, counters, out, (hipStream_t)stream);
 }
 
 // All sixteen counters reach `host_counters` (pinned) through a copy on the

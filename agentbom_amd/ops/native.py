@@ -1557,7 +1557,7 @@ def blast_hops_sized(pkgs32, n_dev, rev: dict, index: dict, agent_index: dict,
 
 # ── Remediation plan (ops/csrc/remediation.hip) ─────────────────────────────
 
-# LDS caps of remed_union_wave_kernel and the install count above which an
+# LDS caps of the remediation tier-1 kernel and the install count above which an
 # item goes straight to the bitmap tier (REMED_*, csrc/remediation.hip);
 # ``abom_remediation_cap`` reports the values the library was built with.
 REMEDIATION_SRV_CAP = 256
@@ -1567,8 +1567,9 @@ REMEDIATION_TL_CAP = 512
 REMEDIATION_T1_INSTALLS = 1024
 # workspace tensors that are all-zero between calls
 REMEDIATION_ZERO_KEYS = ("remed_state", "remed_counters", "remed_pool")
-_REMED_POOL_BYTES = 256 << 20
-_REMED_POOL_SLICES = 256
+# the bitmap pool of the union tiers, whoever uses them
+_UNION_POOL_BYTES = 256 << 20
+_UNION_POOL_SLICES = 256
 _WF_HAS_FIXED = 2
 
 
@@ -1590,6 +1591,53 @@ def _reach_node_span(index: dict) -> int:
             span = max(span, int(index["reach_col"].max().item()) + 1)
         index["node_span"] = span
     return span
+
+
+def _require_union_graph(rev: dict, index: dict, dev) -> None:
+    """The reverse CSR and the per-server reach index, as the union tiers of
+    csrc/abom_union.h read them."""
+    import torch
+
+    _require(rev["row_off"], "rev.row_off", torch.int64, dev)
+    _require(rev["col"], "rev.col", torch.int32, dev)
+    _require(rev["etype"], "rev.etype", torch.uint8, dev, rev["col"].numel())
+    _require(index["reach_off"], "index.reach_off", torch.int32, dev)
+    _require(index["reach_col"], "index.reach_col", torch.int32, dev)
+
+
+def _union_workspace(who: str, ws: dict, prefix: str, index: dict, planes: int, n_groups: int,
+                     n_counters: int, n_matched: int, pool_slices: Optional[int], dev):
+    """The workspace of a per-group analysis that ends in the union tiers:
+    ``<prefix>_state`` (8 words per group), ``<prefix>_counters`` and
+    ``<prefix>_pool`` (``pool_slices`` slices of one bit per reach-index row
+    and ``planes`` planes of one bit per node id), all zeroed on creation;
+    ``<prefix>_matched`` and the pinned ``<prefix>_host_counters``.  Returns
+    (rows, span, pool_slices, state, counters, pool, matched, host)."""
+    import torch
+
+    rows = index["reach_off"].shape[0]
+    span = _reach_node_span(index)
+    slice_words = (rows + 31) // 32 + planes * ((span + 31) // 32)
+    if pool_slices is None:
+        pool_slices = max(1, min(_UNION_POOL_SLICES, _UNION_POOL_BYTES // (4 * slice_words)))
+    if pool_slices < 1:
+        raise ValueError(f"{who}: pool_slices < 1")
+    state = _buf(ws, f"{prefix}_state", 8 * n_groups, torch.int32, dev, zero=True)
+    counters = _buf(ws, f"{prefix}_counters", n_counters, torch.int32, dev, zero=True)
+    pool = _buf(ws, f"{prefix}_pool", pool_slices * slice_words, torch.int32, dev, zero=True)
+    matched = _buf(ws, f"{prefix}_matched", n_matched, torch.int32, dev)
+    host = ws.get(f"{prefix}_host_counters")
+    if host is None:
+        host = ws[f"{prefix}_host_counters"] = torch.zeros(
+            n_counters, dtype=torch.int32, pin_memory=True)
+    return rows, span, pool_slices, state, counters, pool, matched, host
+
+
+def _read_counters(done, host) -> list:
+    """The pinned counters once the copy enqueued before this call has landed."""
+    done.record()
+    done.synchronize()
+    return host.tolist()
 
 
 def _remediation_empty(torch, dev) -> dict:
@@ -1629,11 +1677,7 @@ def remediation_items(pkg_idx, win_idx, scores, item_of, n_items: int, arena: di
     _require(win_idx, "win_idx", torch.int64, dev, F)
     _require(scores, "scores", torch.float32, dev, F)
     _require(item_of, "item_of", torch.int32, dev)
-    _require(rev["row_off"], "rev.row_off", torch.int64, dev)
-    _require(rev["col"], "rev.col", torch.int32, dev)
-    _require(rev["etype"], "rev.etype", torch.uint8, dev, rev["col"].numel())
-    _require(index["reach_off"], "index.reach_off", torch.int32, dev)
-    _require(index["reach_col"], "index.reach_col", torch.int32, dev)
+    _require_union_graph(rev, index, dev)
     windows = arena["windows"]
     W = windows["flags"].numel()
     _require(windows["flags"], "windows.flags", torch.uint8, dev)
@@ -1648,29 +1692,15 @@ def remediation_items(pkg_idx, win_idx, scores, item_of, n_items: int, arena: di
     if F >= 1 << 31:
         raise RuntimeError(f"remediation_items: {F} findings exceed int32")
     lib = load()
-    rows = index["reach_off"].shape[0]
-    span = _reach_node_span(index)
-    slice_words = (rows + 31) // 32 + 3 * ((span + 31) // 32)
-    if pool_slices is None:
-        pool_slices = max(1, min(_REMED_POOL_SLICES, _REMED_POOL_BYTES // (4 * slice_words)))
-    if pool_slices < 1:
-        raise ValueError("remediation_items: pool_slices < 1")
-    state = _buf(ws, "remed_state", 8 * n_items, torch.int32, dev, zero=True)
-    counters = _buf(ws, "remed_counters", 4, torch.int32, dev, zero=True)
-    pool = _buf(ws, "remed_pool", pool_slices * slice_words, torch.int32, dev, zero=True)
-    matched = _buf(ws, "remed_matched", min(n_items, F), torch.int32, dev)
-    host = ws.get("remed_host_counters")
-    if host is None:
-        host = ws["remed_host_counters"] = torch.zeros(4, dtype=torch.int32, pin_memory=True)
+    rows, span, pool_slices, state, counters, pool, matched, host = _union_workspace(
+        "remediation_items", ws, "remed", index, 3, n_items, 4, min(n_items, F), pool_slices, dev)
     rc = lib.abom_remediation_fold(
         _ptr(pkg_idx), _ptr(win_idx), _ptr(scores), F,
         _ptr(item_of), _ptr(arena["severity"]), _ptr(arena["kev"]),
         _ptr(state), _ptr(matched), _ptr(counters), _ptr(host), _stream())
     _check(rc, "abom_remediation_fold")
     done = torch.cuda.Event()
-    done.record()
-    done.synchronize()  # the host read that sizes the outputs
-    M, _, _, NI = host.tolist()
+    M, _, _, NI = _read_counters(done, host)  # the host read that sizes the outputs
     items = torch.sort(matched[:M]).values
     i32 = {k: torch.empty(M, dtype=torch.int32, device=dev)
            for k in ("rep_pkg", "installs", "n_findings", "n_vulns", "max_score", "n_unfixed",
@@ -1703,9 +1733,7 @@ def remediation_items(pkg_idx, win_idx, scores, item_of, n_items: int, arena: di
         _ptr(i32["n_servers"]), _ptr(i32["n_agents"]), _ptr(i32["n_creds"]),
         _ptr(i32["n_tools"]), _stream())
     _check(rc, "abom_remediation_union")
-    done.record()
-    done.synchronize()
-    _, ws["remed_queued"], ws["remed_rounds"], _ = host.tolist()
+    _, ws["remed_queued"], ws["remed_rounds"], _ = _read_counters(done, host)
     out = {"item": items, **i32, **u8, **i64}
     out["max_score"] = out["max_score"].view(torch.float32)
     return out
@@ -1788,7 +1816,7 @@ def remediation_items_join(pkg_idx, win_idx, scores, item_of, arena: dict, rev: 
     return out
 
 
-# LDS caps of toxic_union_wave_kernel and the package count above which an
+# LDS caps of the toxic tier-1 kernel and the package count above which an
 # advisory goes straight to the bitmap tier (TOXIC_*, csrc/toxic.hip);
 # ``abom_toxic_cap`` reports the values the library was built with.
 TOXIC_SRV_CAP = 256
@@ -1890,11 +1918,7 @@ def toxic_combinations(pkg_idx, win_idx, scores, n_creds, arena: dict, tool_lut,
     _require(arena["kev"], "arena.kev", torch.uint8, dev, W)
     _require(arena["impact"], "arena.impact", torch.uint8, dev, W)
     _require(tool_lut, "tool_lut", torch.uint8, dev, 9)
-    _require(rev["row_off"], "rev.row_off", torch.int64, dev)
-    _require(rev["col"], "rev.col", torch.int32, dev)
-    _require(rev["etype"], "rev.etype", torch.uint8, dev, rev["col"].numel())
-    _require(index["reach_off"], "index.reach_off", torch.int32, dev)
-    _require(index["reach_col"], "index.reach_col", torch.int32, dev)
+    _require_union_graph(rev, index, dev)
     rows = index["reach_off"].shape[0]
     _require(table, "table", torch.int32, dev, rows)
     if vuln_of is None:
@@ -1912,20 +1936,9 @@ def toxic_combinations(pkg_idx, win_idx, scores, n_creds, arena: dict, tool_lut,
     if F >= 1 << 31 or V >= 1 << 31:
         raise RuntimeError(f"toxic_combinations: {F} findings / {V} advisories exceed int32")
     lib = load()
-    span = _reach_node_span(index)
-    slice_words = (rows + 31) // 32 + (span + 31) // 32
-    if pool_slices is None:
-        pool_slices = max(1, min(_REMED_POOL_SLICES, _REMED_POOL_BYTES // (4 * slice_words)))
-    if pool_slices < 1:
-        raise ValueError("toxic_combinations: pool_slices < 1")
-    state = _buf(ws, "toxic_state", 8 * V, torch.int32, dev, zero=True)
-    counters = _buf(ws, "toxic_counters", _TOXIC_COUNTERS, torch.int32, dev, zero=True)
-    pool = _buf(ws, "toxic_pool", pool_slices * slice_words, torch.int32, dev, zero=True)
-    matched = _buf(ws, "toxic_matched", min(V, F), torch.int32, dev)
-    host = ws.get("toxic_host_counters")
-    if host is None:
-        host = ws["toxic_host_counters"] = torch.zeros(
-            _TOXIC_COUNTERS, dtype=torch.int32, pin_memory=True)
+    rows, span, pool_slices, state, counters, pool, matched, host = _union_workspace(
+        "toxic_combinations", ws, "toxic", index, 1, V, _TOXIC_COUNTERS, min(V, F), pool_slices,
+        dev)
     vuln_p = _ptr(vuln_of) if vuln_of is not None else None
     patterns = torch.empty(F, dtype=torch.uint8, device=dev)
     combo = torch.empty(F, dtype=torch.float32, device=dev)
@@ -1937,9 +1950,7 @@ def toxic_combinations(pkg_idx, win_idx, scores, n_creds, arena: dict, tool_lut,
         _ptr(state), _ptr(matched), _ptr(counters), _ptr(host), _ptr(patterns), _stream())
     _check(rc, "abom_toxic_fold")
     done = torch.cuda.Event()
-    done.record()
-    done.synchronize()  # the host read that sizes the outputs
-    M, _, _, NH = host[:4].tolist()
+    M, _, _, NH = _read_counters(done, host)[:4]  # the host read that sizes the outputs
     vulns = torch.sort(matched[:M]).values
     i32 = {k: torch.empty(M, dtype=torch.int32, device=dev)
            for k in ("n_findings", "n_packages", "n_servers", "n_agents", "max_score")}
@@ -1971,9 +1982,7 @@ def toxic_combinations(pkg_idx, win_idx, scores, n_creds, arena: dict, tool_lut,
         _ptr(state), _ptr(i32["n_agents"]), _ptr(i32["max_score"]), _ptr(u8["patterns"]),
         _ptr(patterns), _ptr(combo), _ptr(counters), _ptr(host), _stream())
     _check(rc, "abom_toxic_finish")
-    done.record()
-    done.synchronize()
-    totals = host.tolist()
+    totals = _read_counters(done, host)
     ws["toxic_queued"], ws["toxic_rounds"] = totals[1], totals[2]
     per = {"vuln": vulns, **i32, **u8}
     per["max_score"] = per["max_score"].view(torch.float32)

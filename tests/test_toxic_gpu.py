@@ -13,8 +13,9 @@ import pytest
 import torch
 from remediation_cases import ESTATE_ARGS
 from toxic_cases import (
-    HAND_CASES, assert_engine_equals_oracle, device_inputs, engine_reference, many_packages,
-    many_wide, one_advisory_two_waves, oracle, rules, run_at_lane_62, spread, wide_union,
+    HAND_CASES, assert_engine_equals_oracle, device_inputs, engine_reference, full_server_list,
+    many_packages, many_wide, one_advisory_two_waves, oracle, rules, run_at_lane_62, spread,
+    wide_union,
 )
 
 from agentbom_amd.graph.gpu_engine import EstateEngine
@@ -117,6 +118,23 @@ def test_package_threshold():
     case = many_packages(native.TOXIC_T1_PKGS + 1, 3)
     ws: dict = {}
     _assert_same(_run(case, ws)[0], oracle(case))
+    assert ws["toxic_queued"] == 1
+    _assert_workspace_zero(ws)
+
+
+def test_full_server_list_of_the_block_tier():
+    # 1280 servers in one chunk of 256 packages: past the 1024 a block lists,
+    # a thread visits the reach-index row itself (one plane; remediation's
+    # test_install_threshold_and_full_server_list covers three)
+    case = full_server_list()
+    want = oracle(case)
+    # by construction: 256 packages x 5 servers of their own, agents 0 .. 319,
+    # fewer than the sum of the servers' agent lists
+    assert want["vulns"]["n_packages"].tolist() == [256]
+    assert want["vulns"]["n_servers"].tolist() == [1280]
+    assert want["vulns"]["n_agents"].tolist() == [320] and len(case.uses) == 1600
+    ws: dict = {}
+    _assert_same(_run(case, ws)[0], want)
     assert ws["toxic_queued"] == 1
     _assert_workspace_zero(ws)
 

@@ -381,6 +381,24 @@ def many_packages(n_pkgs: int, n_servers: int) -> ToxicCase:
         findings=[(p, 0, 0.5, 0, 0) for p in range(n_pkgs)]))
 
 
+def full_server_list() -> ToxicCase:
+    """One advisory of 256 packages, one chunk of the block tier, package p
+    alone on servers 5p .. 5p + 4: 1280 distinct servers, more than the 1024
+    a block lists per chunk, so the threads that find the list full visit
+    their servers' rows alone.  Server s is used by agent s % 320 and, every
+    fourth one, by agent (s // 4 + 1) % 320 as well: 320 distinct agents, each
+    on four servers or more."""
+    n_pkgs, per, n_agents = 256, 5, 320
+    n_servers = n_pkgs * per
+    return with_counts(ToxicCase(
+        "full_server_list", n_agents=n_agents, n_servers=n_servers, n_tools=1, n_pkgs=n_pkgs,
+        uses=[(s % n_agents, s) for s in range(n_servers)]
+        + [((s // 4 + 1) % n_agents, s) for s in range(0, n_servers, 4)],
+        provides=[(0, 0)], contains=[(per * p + k, p) for p in range(n_pkgs) for k in range(per)],
+        tool_caps=[EXEC], tool_is_db=[0], windows=WINDOWS,
+        findings=[(p, 0, 1.0 + p % 4, p % 2, 0) for p in range(n_pkgs)]))
+
+
 def many_wide(n_wide: int, size: int) -> ToxicCase:
     """``n_wide`` advisories of ``size`` packages each, every package on a
     server of its own; the servers of neighbouring advisories overlap by half."""
